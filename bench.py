@@ -1,8 +1,19 @@
 #!/usr/bin/env python3
-"""bench.py — image-pairs/s of RegressionMatcher.match() at 560->864 on N MI355X (BASELINE.json metric), plus the
+"""bench.py — image-pairs/s of RegressionMatcher.match() at 560->864 on N MI355X (BASELINE.json metric); with --full also the
 HBM roofline of the local_correlation kernel, a CPU baseline timed on the same box and the parity of what is timed.
 
-    python bench.py --gpus N --steps K --warmup W [--workload outdoor|coarse|indoor_sample|tiny] [--pairs P]
+    python bench.py --gpus N --steps K --warmup W [--workload outdoor|coarse|indoor_sample|tiny] [--pairs P] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the result line (`value`, `ms_per_step`, ...).  --full adds every other
+figure of the line: `roofline` (HIP events around each local_correlation launch of the timed steps), and for the default
+workload on one GPU `roofline_pipeline_coherent`, `value_fp32_mode`, `roofline_microbench`, `cpu_baseline`, `parity` and
+`parity_fp16` (runs of their own after the timed region; --no-microbench / --no-cpu skip some of them);
+`--workload indoor_sample` adds `ms_per_step_without_sample`.  Without --full those keys are null.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller (warp, certainty and,
+for indoor_sample, each pair's sampled matches and certainties) as DIR/<name>.npy, float32 (float64 where the path returns
+float64); over 64 MB in all, each array is replaced by the same seeded sample of its elements.  The inputs are a function of
+the arguments alone, so two builds can be compared file by file.
 
 N > 1: when WORLD_SIZE is not set, bench.py launches its own ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py ...`, one rank per GPU, as a child process) and relays rank 0's JSON line; under an external torchrun it is a
@@ -55,7 +66,12 @@ def parse_args(argv=None):
     ap.add_argument("--wire", default="fp32", choices=["fp32", "fp16"], help="dtype of (warp, certainty) on the links of the N>1 gather")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline / parity legs")
     ap.add_argument("--no-microbench", action="store_true", help="skip the standalone local_corr launches (for --pmc passes over the pipeline only)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also measure the roofline, diagnostic and parity figures (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args) -> int:
@@ -97,14 +113,53 @@ INPUTS_NOTE = ("roma_amd.synthetic.synthetic_pair(i): smooth random texture + kn
                "ImageNet-normalised statistics (SURVEY §8(d) prescribes N(0,1) tensors with the same seeds)")
 
 
+def load_synthetic_weights(model, seed=0):
+    """roma_amd.synthetic.load_synthetic_weights with the entries drawn on host_cores() threads (numpy's generator releases the
+    GIL): each entry is a function of (key, shape, seed) alone, so the weights are bit-identical to the serial loader's, and the
+    ~415 M draws no longer take ~10 s of one core at every start."""
+    from concurrent.futures import ThreadPoolExecutor
+    from roma_amd.synthetic import SYNTH_GAINS, synthetic_tensor
+    vit = model.encoder.dinov2_vitl14[0]
+    shapes = {k: v.shape for k, v in model.state_dict().items()}
+    vit_shapes = {"dinov2." + k: v.shape for k, v in vit.state_dict().items()}
+    with ThreadPoolExecutor(host_cores()) as ex:
+        sd = dict(zip(shapes, ex.map(lambda k: synthetic_tensor(k, shapes[k], seed, SYNTH_GAINS), shapes)))
+        vd = dict(zip(vit_shapes, ex.map(lambda k: synthetic_tensor(k, vit_shapes[k], seed), vit_shapes)))
+    model.load_state_dict(sd)
+    vit.load_state_dict({k[len("dinov2."):]: v for k, v in vd.items()})
+    return model
+
+
 def build_model(device, dtype):
     import torch  # noqa: F401
     from roma_amd.model_zoo import build_roma
-    from roma_amd.synthetic import load_synthetic_weights
     model = build_roma((560, 560), upsample_preds=True, amp_dtype=dtype)
     load_synthetic_weights(model, seed=0)
     model.upsample_res = (864, 864)
     return model.to(device).eval()
+
+
+DUMP_BUDGET = 60 << 20        # bytes of array data: 64 MB in all with room for the .npy headers
+
+
+def dump_outputs(out, directory):
+    """What one step returned to its caller, as DIR/<name>.npy: (warp, certainty[, [(matches, certainty) per pair]]).  Over
+    DUMP_BUDGET, each array is replaced by a seeded sample of its flattened elements whose positions depend on the shapes alone."""
+    import numpy as np
+    arrays = {"warp": out[0], "certainty": out[1]}
+    for i, (m, c) in enumerate(out[2] if len(out) > 2 else ()):
+        arrays[f"sample_matches_{i}"], arrays[f"sample_certainty_{i}"] = m, c
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: a.astype(np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        if total > DUMP_BUDGET:
+            keep = a.size * DUMP_BUDGET // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(directory, k + ".npy"), a)
+    log(f"[bench] outputs of the last timed step: {', '.join(sorted(arrays))} -> {directory}"
+        + (f" (seeded sample of {DUMP_BUDGET / total:.3f} of the elements)" if total > DUMP_BUDGET else ""))
 
 
 def run_oracle(images, budget_s=300):
@@ -389,6 +444,8 @@ def stub_main(args, world, rank):
         tt = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     if rank == 0:
         order_ok = all(float(out[0][i * P, 0, 0, 0]) == float(i) for i in range(world))
         print(json.dumps({"metric": "image-pairs/sec at 560->864", "value": world * P * args.steps / elapsed, "unit": "image-pairs/s",
@@ -438,7 +495,7 @@ def main():
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}[args.dtype]
     if args.workload == "tiny":
         dtype = torch.float32                               # TinyRoMa runs fp32 (no autocast in tiny.py:330-367)
-    do_cpu = (rank == 0 and world == 1 and not args.no_cpu and args.workload == "outdoor")
+    do_cpu = (args.full and rank == 0 and world == 1 and not args.no_cpu and args.workload == "outdoor")
     torch.set_grad_enabled(False)
     t0 = time.time()
     torch.set_num_threads(host_cores())
@@ -452,19 +509,24 @@ def main():
             warp, cert = out[0], out[1]
             if backend != "nccl":                       # rehearsal path: gloo gathers host tensors
                 warp, cert = warp.cpu(), cert.cpu()
-            gather_results(warp, cert, world * P, dst=0, wire_dtype=torch.float16 if args.wire == "fp16" else None)
+            got = gather_results(warp, cert, world * P, dst=0, wire_dtype=torch.float16 if args.wire == "fp16" else None)
+            if rank == 0:
+                out = got + tuple(out[2:])
         return out
 
+    t0 = time.time()
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
+    log(f"[bench] rank {rank}: {args.warmup} warm-up steps in {time.time()-t0:.1f}s")
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    ops.TIMER.start()
+    if args.full:
+        ops.TIMER.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -480,9 +542,11 @@ def main():
         n_distinct = len(set(devs))
     else:
         n_distinct = 1
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
 
     eager = getattr(run, "eager", None)
-    if rank == 0 and eager is not None and "hipGraph" in cfg.get("launch", ""):
+    if args.full and rank == 0 and eager is not None and "hipGraph" in cfg.get("launch", ""):
         # A graph replay offers no per-kernel events: the local_corr launches are timed with HIP events over an EAGER run of the
         # same steps (same kernels, same inputs, same streams) right after the timed region.
         n_ev = max(3, min(args.steps, 10))
@@ -497,21 +561,21 @@ def main():
     if rank == 0:
         summ = ops.TIMER.summary()
         roof = None
-        if args.workload == "tiny":
+        if args.full and args.workload == "tiny":
             tc = summ.get("tiny_corr")
             if tc:
                 a = tc["bytes"] / tc["seconds"]              # "bytes" carries FLOPs for this MFMA-bound kernel
                 roof = {"bound": "mfma", "kernel": "tiny_corr_kernel", "achieved": a / 1e12, "peak": MFMA_F32_PEAK / 1e12, "unit": "TFLOP/s",
                         "frac": a / MFMA_F32_PEAK, "traffic": None, "launches": tc["launches"],
                         "avg_launch_us": tc["seconds"] / tc["launches"] * 1e6, "algorithmic_flops_per_launch": tc["bytes"] / tc["launches"]}
-        else:
+        elif args.full:
             lc = summ.get("local_corr")
             if lc:
                 traffic, tnote = measured_traffic() if args.workload == "outdoor" and P == 1 else (None, "collected for the default workload only")
                 roof = lc_roofline(lc, traffic, tnote, "as produced by the timed pipeline (random-init weights => spatially incoherent flow: every "
                                    "pixel gathers its own (2r+2)^2 patch; see roofline_pipeline_coherent / roofline_microbench for coherent flow)")
         coherent = fp32_mode = None
-        if args.workload == "outdoor" and world == 1 and not args.no_microbench and eager is not None:
+        if args.full and args.workload == "outdoor" and world == 1 and not args.no_microbench and eager is not None:
             # (1) the SAME pipeline with the flow entering every refiner replaced by the known warp of the synthetic pair + 0.5 px noise
             # (Decoder.flow_override, diagnostic): the local_corr regime of a trained matcher, inside the pipeline.  Not part of `value`.
             gen = torch.Generator().manual_seed(0)
@@ -555,10 +619,10 @@ def main():
             del m32
             torch.cuda.empty_cache()
         micro = None
-        if not args.no_microbench and args.workload == "outdoor":
+        if args.full and not args.no_microbench and args.workload == "outdoor":
             micro = local_corr_microbench(device, dtype, P)
         extra = {}
-        if args.workload == "indoor_sample":
+        if args.full and args.workload == "indoor_sample":
             # the same pairs without the sampling stage, for the "with and without sampling" report of SURVEY §8(d)
             A_lo, B_lo, A_hi, B_hi = resident
             torch.cuda.synchronize()

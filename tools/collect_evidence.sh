@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 say() { echo "[$(date +%T)] $*" | tee -a $O/progress_$PART.txt; }
 if [ "$PART" = "a" ]; then
 say "kernel trace of bench.py"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu --no-microbench > $O/bench_prof.json 2> $O/bench_prof.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu --no-microbench > $O/bench_prof.json 2> $O/bench_prof.err
 python3 $R/tools/trace_last_step.py $(ls $O/prof_bench/*/*kernel_trace.csv | head -1) > $O/bench_last_step.md
 cp $(ls $O/prof_bench/*/*kernel_stats.csv | head -1) $O/bench_kernel_stats.csv
 rm -f $O/prof_bench/*/*kernel_trace.csv $O/prof_bench/*/*agent_info.csv
@@ -41,8 +41,8 @@ bash tools/pmc_bench_traffic.sh > $O/traffic.log 2>&1
 cp gpurun_out/bench_line_final.json $O/bench_line.json 2>/dev/null
 cp gpurun_out/local_corr_traffic.json $O/ 2>/dev/null
 say "other bench lines"
-python3 bench.py --pairs 8 --no-cpu --no-microbench > $O/bench_pairs8.json 2>> $O/bench_line.err
-python3 bench.py --workload coarse --no-cpu --no-microbench > $O/bench_coarse.json 2>> $O/bench_line.err
-python3 bench.py --workload indoor_sample --no-cpu --no-microbench > $O/bench_indoor_sample.json 2>> $O/bench_line.err
-python3 bench.py --workload tiny --no-cpu --no-microbench > $O/bench_tiny.json 2>> $O/bench_line.err
+python3 bench.py --full --pairs 8 --no-cpu --no-microbench > $O/bench_pairs8.json 2>> $O/bench_line.err
+python3 bench.py --full --workload coarse --no-cpu --no-microbench > $O/bench_coarse.json 2>> $O/bench_line.err
+python3 bench.py --full --workload indoor_sample --no-cpu --no-microbench > $O/bench_indoor_sample.json 2>> $O/bench_line.err
+python3 bench.py --full --workload tiny --no-cpu --no-microbench > $O/bench_tiny.json 2>> $O/bench_line.err
 say "done (b)"

@@ -13,4 +13,4 @@ timeout -k 5 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -
 python3 $R/tools/pmc_traffic.py $O/bench_fetch $O/bench_write 44550979.2 > $R/gpurun_out/local_corr_traffic.json
 cp $R/gpurun_out/local_corr_traffic.json $R/profiles/local_corr_traffic.json
 cd $R
-python3 bench.py > $R/gpurun_out/bench_line_final.json 2> $R/gpurun_out/bench_line_final.err
+python3 bench.py --full > $(dirname $O)/bench_line_final.json 2> $(dirname $O)/bench_line_final.err
