@@ -283,6 +283,31 @@ int roma_jpeg_info(const void* data, long nbytes, int* info);
 int roma_jpeg_entropy_decode(const void* data, long nbytes, int16_t* coef, uint16_t* qt);
 int roma_jpeg_reconstruct(const int16_t* coef, const uint16_t* qt, void* planes, void* rgb, const int* info, void* stream);
 
+/* Robust two-view geometry (RANSAC with MSAC scoring and least-squares local optimisation) — replaces the
+ * estimator callers run on the output of match -> sample -> to_pixel_coordinates:
+ *   kind 0, fundamental matrix (7-point):  cv2.findFundamentalMat(..., USAC_MAGSAC, maxIters=10000) of demo/demo_fundamental.py:28-34
+ *                                          and of estimate_pose_uncalibrated, romatch/utils/utils.py:54-62;
+ *   kind 1, homography (4-point DLT):      cv2.findHomography(..., RANSAC) of romatch/benchmarks/hpatches_sequences_homog_benchmark.py:72-86.
+ * xa, xb: (P,N,2) fp64 pixel coordinates of P pairs.  `iters` minimal samples per pair, all drawn and scored (no early stop);
+ * the draw is a pure function of (seed, p0 + p, sample), p0 = index of this call's first pair in a larger batch (geometry.hip
+ * pins the hash).  threshold in pixels: inlier when the squared error (Sampson for F, forward transfer for H) < threshold^2.
+ * Workspace: ws of at least roma_ransac_workspace(kind, P, N, iters, NULL) bytes, owned by the caller; the library allocates nothing.
+ *
+ * roma_ransac_workspace: host function; returns the workspace size in bytes (<0 on bad arguments) and, if offsets != NULL, the
+ *   byte offsets of its 9 regions: [0] per-pair normalisation (P,8) fp64 = (cx, cy, s, 0) of A then of B, x_hat = (x - c) * s;
+ *   [1] normalised points (P,N,4) fp32; [2] samples (P,iters,S) int32, S = 7 / 4, -1 = invalid sample; [3] minimal models
+ *   (P,iters,R,3,3) fp64 in normalised coordinates, R = 3 / 1 slots per sample; [4] valid (P,iters,R) int32; [5], [6] the scoring
+ *   slab; [7] MSAC cost per slot (P,iters,R) fp64 (+inf when invalid); [8] inlier count per slot (P,iters,R) int32.
+ * roma_ransac_hypotheses: normalisation, samples, minimal solvers and scoring into the workspace (regions 0-8).
+ * roma_ransac_select: the lowest-cost slot per pair, lo_iters rounds of local optimisation, de-normalisation.  model: (P,3,3) fp64
+ *   (F: unit Frobenius norm, largest-magnitude entry positive; H: H[2,2] = 1), all zeros when no sample gave a model;
+ *   mask: (P,N) uint8 inliers of the returned model. */
+long roma_ransac_workspace(int kind, int P, int N, int iters, long* offsets);
+int roma_ransac_hypotheses(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, unsigned seed,
+                           int p0, void* ws, long ws_bytes, void* stream);
+int roma_ransac_select(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int lo_iters,
+                       const void* ws, long ws_bytes, double* model, unsigned char* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,8 +61,12 @@ SIGNATURES = {
                           c_float, c_float, c_void_p],
     "roma_pointwise_small": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_void_p],
     "roma_tiny_corr_posembed": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "roma_ransac_workspace": [c_int, c_int, c_int, c_int, c_void_p],
+    "roma_ransac_hypotheses": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, ctypes.c_uint, c_int, c_void_p, c_long, c_void_p],
+    "roma_ransac_select": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_long, c_void_p, c_void_p,
+                           c_void_p],
 }
-_RESTYPES = {"roma_last_error": c_char_p}
+_RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long}
 
 _lib = None
 

@@ -1,0 +1,176 @@
+"""Robust two-view geometry on the device: the estimator that follows match -> sample -> to_pixel_coordinates.
+
+`find_fundamental` replaces cv2.findFundamentalMat (demo/demo_fundamental.py:28-34, estimate_pose_uncalibrated in
+romatch/utils/utils.py:54-62) and `find_homography` replaces cv2.findHomography (hpatches_sequences_homog_benchmark.py:72-86).
+RANSAC with a fixed number of minimal samples (7-point F, 4-point DLT H, fp64, Hartley-normalised), MSAC scoring in fp32,
+lowest cost wins, then least-squares local optimisation (kernels in csrc/geometry.hip).  Every sample is
+drawn and scored; there is no early stop.  The draw is a pure function of the seed (tests/geometry_ref.py restates it).
+No host synchronisation: a call can be captured in a hipGraph.  Tensors must live on a ROCm device; there is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _lib
+from ._lib import check
+from .ops import _need_gpu, _stream
+
+KIND_F, KIND_H = 0, 1
+_SMIN = {KIND_F: 7, KIND_H: 4}
+_SLOTS = {KIND_F: 3, KIND_H: 1}
+_WORKSPACE_LIMIT = 192 << 20          # workspace bytes of one call; larger batches run in chunks of pairs that share it
+
+
+def _kind(model):
+    if model in ("fundamental", "F", KIND_F):
+        return KIND_F
+    if model in ("homography", "H", KIND_H):
+        return KIND_H
+    raise ValueError(f"unknown model {model!r}: 'fundamental' or 'homography'")
+
+
+def _points(x_A, x_B, kind):
+    """(N,2) or (P,N,2) fp32/fp64 device tensors -> contiguous (P,N,2) fp64, single-pair flag."""
+    _need_gpu(x_A, x_B)
+    if x_A.shape != x_B.shape:
+        raise ValueError(f"x_A {tuple(x_A.shape)} and x_B {tuple(x_B.shape)} differ in shape")
+    if x_A.dim() not in (2, 3) or x_A.shape[-1] != 2:
+        raise ValueError(f"expected (N,2) or (P,N,2) pixel coordinates, got {tuple(x_A.shape)}")
+    for t in (x_A, x_B):
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"pixel coordinates must be float32 or float64, got {t.dtype}")
+    single = x_A.dim() == 2
+    P, N = (1, x_A.shape[0]) if single else (x_A.shape[0], x_A.shape[1])
+    if N < _SMIN[kind]:
+        raise ValueError(f"{N} matches, the minimal sample needs {_SMIN[kind]}")
+    if P < 1:
+        raise ValueError("empty batch")
+    xa = x_A.reshape(P, N, 2).to(torch.float64).contiguous()
+    xb = x_B.reshape(P, N, 2).to(torch.float64).contiguous()
+    return xa, xb, single
+
+
+def _seed(seed):
+    # like RegressionMatcher.sample: torch's CPU generator, no device sync
+    return int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed) & 0xFFFFFFFF
+
+
+def _args(threshold, max_iters, lo_iters):
+    if not threshold > 0:
+        raise ValueError(f"threshold must be positive, got {threshold}")
+    if int(max_iters) < 1:
+        raise ValueError(f"max_iters must be positive, got {max_iters}")
+    if int(lo_iters) < 0:
+        raise ValueError(f"lo_iters must be >= 0, got {lo_iters}")
+
+
+def workspace_layout(kind, P, N, iters):
+    """(total bytes, [9 region offsets]) of the workspace (include/roma_hip.h, roma_ransac_workspace)."""
+    off = (ctypes.c_long * 9)()
+    total = _lib.load().roma_ransac_workspace(kind, P, N, iters, ctypes.cast(off, ctypes.c_void_p))
+    if total < 0:
+        check(int(total), "roma_ransac_workspace")
+    return int(total), list(off)
+
+
+def _chunks(kind, P, N, iters):
+    """Pair ranges [a, b) of one call: as few as keep a chunk's workspace within _WORKSPACE_LIMIT, of balanced size."""
+    per_pair, _ = workspace_layout(kind, 1, N, iters)
+    most = max(1, _WORKSPACE_LIMIT // per_pair)
+    n = -(-P // most)
+    step = -(-P // n)
+    return [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
+
+
+def _hypotheses(xa, xb, kind, threshold, iters, seed, p0, ws):
+    P, N = xa.shape[0], xa.shape[1]
+    check(_lib.load().roma_ransac_hypotheses(kind, xa.data_ptr(), xb.data_ptr(), P, N, iters, float(threshold), seed, p0,
+                                             ws.data_ptr(), ws.numel(), _stream()), "roma_ransac_hypotheses")
+
+
+def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters):
+    _args(threshold, max_iters, lo_iters)
+    xa, xb, single = _points(x_A, x_B, kind)
+    P, N = xa.shape[0], xa.shape[1]
+    iters, seed = int(max_iters), _seed(seed)
+    model = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
+    mask = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
+    lib = _lib.load()
+    chunks = _chunks(kind, P, N, iters)
+    # one workspace, sized for the widest chunk, serves every chunk in stream order (a narrower chunk's layout is no larger)
+    total, _ = workspace_layout(kind, max(b - a for a, b in chunks), N, iters)
+    ws = torch.empty((total,), dtype=torch.uint8, device=xa.device)
+    for a, b in chunks:
+        ca, cb = xa[a:b], xb[a:b]
+        _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws)
+        check(lib.roma_ransac_select(kind, ca.data_ptr(), cb.data_ptr(), b - a, N, iters, float(threshold), int(lo_iters),
+                                     ws.data_ptr(), total, model[a:b].data_ptr(), mask[a:b].data_ptr(), _stream()),
+              "roma_ransac_select")
+    mask = mask.bool()
+    return (model[0], mask[0]) if single else (model, mask)
+
+
+def find_fundamental(x_A, x_B, threshold=3.0, max_iters=10000, seed=None, lo_iters=3):
+    """Fundamental matrix F (x_B^T F x_A = 0) of pixel correspondences x_A <-> x_B, (N,2) or (P,N,2), fp32/fp64 on the device.
+    Returns (F fp64 (3,3) or (P,3,3), unit Frobenius norm, largest-magnitude entry positive; inlier mask bool (N,) or (P,N)):
+    Sampson error below threshold (pixels).  All zeros and an empty mask when no sample gives a model."""
+    return _estimate(x_A, x_B, KIND_F, threshold, max_iters, seed, lo_iters)
+
+
+def find_homography(x_A, x_B, threshold=3.0, max_iters=2000, seed=None, lo_iters=3):
+    """Homography H (x_B ~ H x_A) of pixel correspondences, shapes as find_fundamental.  Returns (H fp64 with H[2,2] = 1 — unit
+    Frobenius norm if |H[2,2]| < 1e-12 |H| —, inlier mask: forward transfer error below threshold)."""
+    return _estimate(x_A, x_B, KIND_H, threshold, max_iters, seed, lo_iters)
+
+
+def _view(ws, off, i, dtype, shape):
+    n = 1
+    for s in shape:
+        n *= s
+    item = torch.empty((), dtype=dtype).element_size()
+    return ws[off[i]:off[i] + n * item].view(dtype).reshape(shape)
+
+
+def minimal_samples(x_A, x_B, model="fundamental", max_iters=10000, seed=0):
+    """The indices each minimal sample draws: (P, max_iters, s) int32, s = 7 (F) / 4 (H), a row of -1 for an invalid sample.
+    An inspection helper like score_hypotheses, with its batch limit."""
+    return score_hypotheses(x_A, x_B, model, 3.0, max_iters, seed)["samples"]
+
+
+def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=10000, seed=0):
+    """Every hypothesis of one call, before selection (batched (P,...) shapes even for a single pair):
+    samples (P,iters,s) int32; models (P,iters,R,3,3) fp64 in normalised coordinates (unit Frobenius norm), R = 3 root slots
+    for F, 1 for H; valid (P,iters,R) bool; count (P,iters,R) int32 inliers; cost (P,iters,R) fp64 MSAC cost (+inf if invalid);
+    T_A, T_B (P,3,3) fp64 normalising transforms (x_hat = T x).  A model in pixels is T_B^T F^ T_A or T_B^-1 H^ T_A.
+    Pair p draws what it draws in find_fundamental / find_homography with the same seed.  An inspection helper: it keeps the
+    whole batch's workspace and returns every slot, so it refuses a batch whose workspace exceeds the chunk limit of the
+    estimators (192 MiB: about 35 pairs at N = 10 000 and 10 000 F samples) — call it on fewer pairs."""
+    kind = _kind(model)
+    _args(threshold, max_iters, 0)
+    xa, xb, _ = _points(x_A, x_B, kind)
+    P, N, iters = xa.shape[0], xa.shape[1], int(max_iters)
+    total, off = workspace_layout(kind, P, N, iters)
+    if total > _WORKSPACE_LIMIT:
+        raise ValueError(f"score_hypotheses: {P} pairs need a {total >> 20} MiB workspace, over the {_WORKSPACE_LIMIT >> 20} MiB "
+                         "limit; call it on fewer pairs")
+    ws = torch.empty((total,), dtype=torch.uint8, device=xa.device)
+    _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws)
+    S, R = _SMIN[kind], _SLOTS[kind]
+    norm = _view(ws, off, 0, torch.float64, (P, 2, 4))
+    T = torch.zeros((P, 2, 3, 3), dtype=torch.float64, device=xa.device)
+    T[:, :, 0, 0] = norm[:, :, 2]
+    T[:, :, 1, 1] = norm[:, :, 2]
+    T[:, :, 0, 2] = -norm[:, :, 2] * norm[:, :, 0]
+    T[:, :, 1, 2] = -norm[:, :, 2] * norm[:, :, 1]
+    T[:, :, 2, 2] = 1.0
+    return {
+        "samples": _view(ws, off, 2, torch.int32, (P, iters, S)).clone(),
+        "models": _view(ws, off, 3, torch.float64, (P, iters, R, 3, 3)).clone(),
+        "valid": _view(ws, off, 4, torch.int32, (P, iters, R)) != 0,
+        "cost": _view(ws, off, 7, torch.float64, (P, iters, R)).clone(),
+        "count": _view(ws, off, 8, torch.int32, (P, iters, R)).clone(),
+        "T_A": T[:, 0].clone(),
+        "T_B": T[:, 1].clone(),
+    }
