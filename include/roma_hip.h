@@ -308,6 +308,35 @@ int roma_ransac_hypotheses(int kind, const double* xa, const double* xb, int P, 
 int roma_ransac_select(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int lo_iters,
                        const void* ws, long ws_bytes, double* model, unsigned char* mask, void* stream);
 
+/* Calibrated two-view geometry — replaces estimate_pose of the reference (romatch/utils/utils.py:31-52:
+ * cv2.findEssentialMat on calibrated points, then cv2.recoverPose), which its MegaDepth-1500 and ScanNet-1500 benchmarks call.
+ * xa, xb: (P,N,2) fp64 PIXEL coordinates; Ka, Kb: (P,3,3) fp64 intrinsics, upper triangular with last row 0 0 1.  The estimator
+ * works on x_hat = K^-1 x (no Hartley normalisation); `threshold` is in those calibrated units (the reference's norm_thresh): inlier
+ * when the Sampson error < threshold^2.  `iters` 5-point samples per pair, all drawn and scored, up to 10 models each; the draw is
+ * the hash of the RANSAC block above with stage 4 (essential.hip pins the solver and its tolerances).  A K with fx * fy == 0 or a
+ * non-finite entry makes every sample of its pair invalid.  The library allocates nothing.
+ *
+ * roma_essential_workspace: host function; the workspace size in bytes (<0 on bad arguments) and, if offsets != NULL, the byte
+ *   offsets of its 10 regions: [0]-[8] as roma_ransac_workspace with S = 5 and R = 10 ([0] is (0, 0, 1, 0) twice; [1] and [3] are in
+ *   calibrated coordinates), [9] calibrated points (P,N,4) fp64 = (xa, ya, xb, yb), NaN where a match is not usable.
+ * roma_essential_hypotheses: calibration, samples, 5-point solver and MSAC scoring into the workspace (regions 0-9).
+ * roma_essential_select: the lowest-cost slot per pair, then lo_iters rounds of least squares on the inliers projected onto the
+ *   essential manifold, each kept only if the cost drops.  E: (P,3,3) fp64 in calibrated coordinates (x_hat_B^T E x_hat_A = 0),
+ *   singular values (1, 1, 0) / sqrt 2, largest-magnitude entry positive, all zeros when no sample gave a model; mask: (P,N) uint8.
+ * roma_recover_pose: the four (R, t) of E — from roma_essential_select, or K_B^T F K_A — and the cheirality vote: for each
+ *   candidate, the matches of mask_in ((P,N) uint8, NULL = all) whose least-squares depths in lambda_B x_B = lambda_A R x_A + t are
+ *   finite and positive in both cameras; the candidate with the most wins (lowest index on ties, order (W,+) (W,-) (W^T,+) (W^T,-)).
+ *   R: (P,3,3), t: (P,3) unit, count: (P) int32 votes of the winner, mask_out: (P,N) uint8 = mask_in narrowed to the matches that
+ *   voted for it (what cv2.recoverPose leaves in its mask).  A zero or non-finite E (or K): R = I, t = 0, count 0, empty mask. */
+long roma_essential_workspace(int P, int N, int iters, long* offsets);
+int roma_essential_hypotheses(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N, int iters,
+                              float threshold, unsigned seed, int p0, void* ws, long ws_bytes, void* stream);
+int roma_essential_select(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N, int iters,
+                          float threshold, int lo_iters, const void* ws, long ws_bytes, double* E, unsigned char* mask, void* stream);
+int roma_recover_pose(const double* xa, const double* xb, const double* Ka, const double* Kb, const double* E,
+                      const unsigned char* mask_in, int P, int N, double* R, double* t, int* count, unsigned char* mask_out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

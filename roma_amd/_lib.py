@@ -65,8 +65,15 @@ SIGNATURES = {
     "roma_ransac_hypotheses": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, ctypes.c_uint, c_int, c_void_p, c_long, c_void_p],
     "roma_ransac_select": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_long, c_void_p, c_void_p,
                            c_void_p],
+    "roma_essential_workspace": [c_int, c_int, c_int, c_void_p],
+    "roma_essential_hypotheses": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, ctypes.c_uint, c_int, c_void_p,
+                                  c_long, c_void_p],
+    "roma_essential_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_long, c_void_p,
+                              c_void_p, c_void_p],
+    "roma_recover_pose": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_void_p],
 }
-_RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long}
+_RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long, "roma_essential_workspace": c_long}
 
 _lib = None
 

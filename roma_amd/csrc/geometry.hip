@@ -24,25 +24,10 @@
 // Rank test of the minimal systems: Gaussian elimination with partial pivoting; a pivot with |pivot| <= 1e-10 * (largest
 // |entry| of the system) rejects the sample.  H samples are also rejected when any 3 of the 4 points are collinear in either
 // image: |(b - a) x (c - a)| <= 1e-6 |b - a| |c - a| (normalised coordinates).
-#include "common.h"
+#include "ransac_common.h"
 
 namespace roma {
 namespace {
-
-constexpr int KIND_F = 0, KIND_H = 1;
-constexpr int CHUNK = 1024;             // points per scoring workgroup (the slab's chunk)
-constexpr double PIVOT_TOL = 1e-10;
-constexpr double COLLINEAR_TOL = 1e-6;
-constexpr int JACOBI_SWEEPS = 10;
-
-__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return h;
-}
-
-template <int KIND> struct Kind;
-template <> struct Kind<KIND_F> { static constexpr int S = 7, R = 3, LO_MIN = 8; };
-template <> struct Kind<KIND_H> { static constexpr int S = 4, R = 1, LO_MIN = 4; };
 
 // ---------------------------------------------------------------------------------------------------------------- normalise
 // norm[p*8 + img*4 + {0,1,2}] = (cx, cy, s): x_hat = (x - c) * s.
@@ -98,10 +83,6 @@ __global__ __launch_bounds__(256) void normalize_kernel(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------ minimal solvers (fp64)
-__device__ __forceinline__ double det3(const double* m) {
-  return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-}
-
 // f2 + a * (f1 - f2), determinant
 __device__ __forceinline__ double det_mix(const double* f1, const double* f2, double a) {
   double m[9];
@@ -163,60 +144,6 @@ __device__ __forceinline__ int cubic_roots(double c3, double c2, double c1, doub
   r0 = newton2(c3, c2, c1, c0, r0);
   if (n == 3) { r1 = newton2(c3, c2, c1, c0, r1); r2 = newton2(c3, c2, c1, c0, r2); }
   return n;
-}
-
-__device__ __forceinline__ void unit_frobenius(double* m) {
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) s += m[i] * m[i];
-  const double inv = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) m[i] *= inv;
-}
-
-// Forward elimination with partial pivoting of the ROWS x 9 system, fully unrolled (rows are swapped by conditional selects, so
-// every index is a compile-time constant and A stays in registers).  Returns false when a pivot fails the relative tolerance.
-template <int ROWS> __device__ __forceinline__ bool eliminate(double (&A)[ROWS][9]) {
-  double scale = 0.0;
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-#pragma unroll
-    for (int c = 0; c < 9; ++c) scale = fmax(scale, fabs(A[r][c]));
-  bool ok = scale > 0.0;
-#pragma unroll
-  for (int c = 0; c < ROWS; ++c) {
-#pragma unroll
-    for (int r = c + 1; r < ROWS; ++r) {
-      const bool sw = fabs(A[r][c]) > fabs(A[c][c]);
-#pragma unroll
-      for (int j = c; j < 9; ++j) {
-        const double t = A[c][j];
-        A[c][j] = sw ? A[r][j] : t;
-        A[r][j] = sw ? t : A[r][j];
-      }
-    }
-    const double piv = A[c][c];
-    ok = ok && fabs(piv) > PIVOT_TOL * scale;
-    const double inv = piv != 0.0 ? 1.0 / piv : 0.0;
-#pragma unroll
-    for (int r = c + 1; r < ROWS; ++r) {
-      const double f = A[r][c] * inv;
-#pragma unroll
-      for (int j = c + 1; j < 9; ++j) A[r][j] = __builtin_fma(-f, A[c][j], A[r][j]);
-    }
-  }
-  return ok;
-}
-
-// x[k] for k < ROWS from the upper-triangular system, with x[ROWS..8] given
-template <int ROWS> __device__ __forceinline__ void back_substitute(const double (&A)[ROWS][9], double* x) {
-#pragma unroll
-  for (int k = ROWS - 1; k >= 0; --k) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = k + 1; j < 9; ++j) s = __builtin_fma(A[k][j], x[j], s);
-    x[k] = -s / A[k][k];
-  }
 }
 
 __device__ __forceinline__ bool collinear(double ax, double ay, double bx, double by, double cx, double cy) {
@@ -354,160 +281,6 @@ __global__ __launch_bounds__(128) void minimal_kernel(const double* __restrict__
 #pragma unroll
     for (int i = 0; i < 9; ++i) models[((size_t)t * R + r) * 9 + i] = mdl[r][i];
   }
-}
-
-// --------------------------------------------------------------------------------------------------------------- scoring (fp32)
-// Squared error in pixels of one normalised point (xa, ya, xb, yb) under a normalised model m.  F: Sampson error, with
-// ka = sA^2, kb = sB^2.  H: forward transfer error, with kb = 1 / sB^2 (ka unused).  NaN / inf -> not an inlier.
-template <int KIND>
-__device__ __forceinline__ float point_error(const float* m, float4 q, float ka, float kb) {
-  if constexpr (KIND == KIND_F) {
-    const float fx0 = __builtin_fmaf(m[0], q.x, __builtin_fmaf(m[1], q.y, m[2]));
-    const float fx1 = __builtin_fmaf(m[3], q.x, __builtin_fmaf(m[4], q.y, m[5]));
-    const float fx2 = __builtin_fmaf(m[6], q.x, __builtin_fmaf(m[7], q.y, m[8]));
-    const float ft0 = __builtin_fmaf(m[0], q.z, __builtin_fmaf(m[3], q.w, m[6]));
-    const float ft1 = __builtin_fmaf(m[1], q.z, __builtin_fmaf(m[4], q.w, m[7]));
-    const float num = __builtin_fmaf(q.z, fx0, __builtin_fmaf(q.w, fx1, fx2));
-    const float den = __builtin_fmaf(kb, __builtin_fmaf(fx0, fx0, fx1 * fx1), ka * __builtin_fmaf(ft0, ft0, ft1 * ft1));
-    return num * num / den;
-  } else {
-    const float hx = __builtin_fmaf(m[0], q.x, __builtin_fmaf(m[1], q.y, m[2]));
-    const float hy = __builtin_fmaf(m[3], q.x, __builtin_fmaf(m[4], q.y, m[5]));
-    const float hw = __builtin_fmaf(m[6], q.x, __builtin_fmaf(m[7], q.y, m[8]));
-    const float iw = 1.0f / hw;
-    const float dx = __builtin_fmaf(-hx, iw, q.z), dy = __builtin_fmaf(-hy, iw, q.w);
-    return __builtin_fmaf(dx, dx, dy * dy) * kb;
-  }
-}
-
-template <int KIND> __device__ __forceinline__ void error_scales(const double* nrm, float& ka, float& kb) {
-  const double sA = nrm[2], sB = nrm[6];
-  ka = (float)(sA * sA);
-  kb = KIND == KIND_F ? (float)(sB * sB) : (float)(1.0 / (sB * sB));
-}
-
-// slab_cost / slab_cnt: (P, S, M) with M = iters * R slots and S = ceil(N / CHUNK) chunks
-template <int KIND>
-__global__ __launch_bounds__(256) void score_kernel(const float4* __restrict__ pts, const double* __restrict__ norm,
-                                                    const double* __restrict__ models, const int* __restrict__ valid, int N, int M,
-                                                    float t2, float* __restrict__ slab_cost, int* __restrict__ slab_cnt) {
-  __shared__ float4 sp[CHUNK];
-  const int p = blockIdx.z, s = blockIdx.y, S = gridDim.y;
-  const int i0 = s * CHUNK, n = min(CHUNK, N - i0);
-  const float4* src = pts + (size_t)p * N + i0;
-  for (int i = threadIdx.x; i < n; i += 256) sp[i] = src[i];
-  __syncthreads();
-  const int m = blockIdx.x * 256 + threadIdx.x;
-  if (m >= M) return;
-  const size_t slot = (size_t)p * M + m;
-  float cost = 0.f;
-  int cnt = 0;
-  if (valid[slot]) {
-    float md[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) md[i] = (float)models[slot * 9 + i];
-    float ka, kb;
-    error_scales<KIND>(norm + p * 8, ka, kb);
-    for (int j = 0; j < n; ++j) {
-      const float e = point_error<KIND>(md, sp[j], ka, kb);
-      const bool in = e < t2;
-      cnt += in ? 1 : 0;
-      cost += in ? e : t2;
-    }
-  }
-  const size_t o = ((size_t)p * S + s) * M + m;
-  slab_cost[o] = cost;
-  slab_cnt[o] = cnt;
-}
-
-__global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ slab_cost, const int* __restrict__ slab_cnt,
-                                                     const int* __restrict__ valid, int P, int M, int S, double* __restrict__ cost,
-                                                     int* __restrict__ count) {
-  const long t = (long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (long)P * M) return;
-  const int p = (int)(t / M), m = (int)(t % M);
-  double c = 0.0;
-  int n = 0;
-  for (int s = 0; s < S; ++s) {
-    const size_t o = ((size_t)p * S + s) * M + m;
-    c += (double)slab_cost[o];
-    n += slab_cnt[o];
-  }
-  const bool v = valid[t] != 0;
-  cost[t] = v ? c : INFINITY;
-  count[t] = v ? n : 0;
-}
-
-// ---------------------------------------------------------------------------------------------- selection + local optimisation
-// Cost (fp32 errors, fp64 sum in a fixed tree) and inlier count of the model in LDS `mdl` over the pair's N points.
-template <int KIND>
-__device__ void block_score(const double* mdl, const float4* pq, int N, float ka, float kb, float t2, double* dred, int* ired,
-                            double& cost, int& cnt) {
-  const int tid = threadIdx.x;
-  float m[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) m[i] = (float)mdl[i];
-  double c = 0.0;
-  int n = 0;
-  for (int i = tid; i < N; i += 256) {
-    const float e = point_error<KIND>(m, pq[i], ka, kb);
-    const bool in = e < t2;
-    n += in ? 1 : 0;
-    c += (double)(in ? e : t2);
-  }
-  dred[tid] = c;
-  ired[tid] = n;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) { dred[tid] += dred[tid + o]; ired[tid] += ired[tid + o]; }
-    __syncthreads();
-  }
-  cost = dred[0];
-  cnt = ired[0];
-  __syncthreads();
-}
-
-// Cyclic Jacobi on the symmetric n x n matrix A (LDS, leading dimension 9), eigenvectors into the columns of V (LDS, set to the
-// identity by the caller).  Lane k < n owns row k; two barriers per rotation.  Every thread of the block calls it.
-__device__ void jacobi_lds(double* A, double* V, int n) {
-  const int k = threadIdx.x;
-  for (int sw = 0; sw < JACOBI_SWEEPS; ++sw) {
-    for (int p = 0; p < n - 1; ++p) {
-      for (int q = p + 1; q < n; ++q) {
-        const double app = A[p * 9 + p], aqq = A[q * 9 + q], apq = A[p * 9 + q];
-        double akp = 0.0, akq = 0.0, vkp = 0.0, vkq = 0.0;
-        if (k < n) { akp = A[k * 9 + p]; akq = A[k * 9 + q]; vkp = V[k * 9 + p]; vkq = V[k * 9 + q]; }
-        __syncthreads();
-        if (apq != 0.0 && k < n) {
-          const double theta = (aqq - app) / (2.0 * apq);
-          const double t = fabs(theta) > 1e150 ? 0.5 / theta : (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-          if (k == p) {
-            A[p * 9 + p] = app - t * apq;
-            A[p * 9 + q] = 0.0;
-            A[q * 9 + p] = 0.0;
-          } else if (k == q) {
-            A[q * 9 + q] = aqq + t * apq;
-          } else {
-            const double nkp = c * akp - s * akq, nkq = s * akp + c * akq;
-            A[k * 9 + p] = nkp; A[p * 9 + k] = nkp;
-            A[k * 9 + q] = nkq; A[q * 9 + k] = nkq;
-          }
-          V[k * 9 + p] = c * vkp - s * vkq;
-          V[k * 9 + q] = s * vkp + c * vkq;
-        }
-        __syncthreads();
-      }
-    }
-  }
-}
-
-// index of the smallest diagonal entry (lowest index on ties)
-__device__ __forceinline__ int argmin_diag(const double* A, int n) {
-  int j = 0;
-  for (int i = 1; i < n; ++i)
-    if (A[i * 9 + i] < A[j * 9 + j]) j = i;
-  return j;
 }
 
 template <int KIND>

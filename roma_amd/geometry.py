@@ -6,6 +6,10 @@ RANSAC with a fixed number of minimal samples (7-point F, 4-point DLT H, fp64, H
 lowest cost wins, then least-squares local optimisation (kernels in csrc/geometry.hip).  Every sample is
 drawn and scored; there is no early stop.  The draw is a pure function of the seed (tests/geometry_ref.py restates it).
 No host synchronisation: a call can be captured in a hipGraph.  Tensors must live on a ROCm device; there is no CPU path.
+
+`find_essential`, `recover_pose`, `estimate_pose` and `estimate_pose_uncalibrated` are the calibrated counterpart (csrc/essential.hip):
+the 5-point solver on K^-1 x, the same scoring and selection, local optimisation on the essential manifold, and the cheirality
+vote of cv2.recoverPose — what the reference's pose benchmarks run per pair on the host (romatch/utils/utils.py:12-76).
 """
 from __future__ import annotations
 
@@ -18,8 +22,9 @@ from ._lib import check
 from .ops import _need_gpu, _stream
 
 KIND_F, KIND_H = 0, 1
-_SMIN = {KIND_F: 7, KIND_H: 4}
-_SLOTS = {KIND_F: 3, KIND_H: 1}
+KIND_E = 2                            # this module's name for the essential estimator; the C ABI has entry points of its own for it
+_SMIN = {KIND_F: 7, KIND_H: 4, KIND_E: 5}
+_SLOTS = {KIND_F: 3, KIND_H: 1, KIND_E: 10}
 _WORKSPACE_LIMIT = 192 << 20          # workspace bytes of one call; larger batches run in chunks of pairs that share it
 
 
@@ -28,7 +33,9 @@ def _kind(model):
         return KIND_F
     if model in ("homography", "H", KIND_H):
         return KIND_H
-    raise ValueError(f"unknown model {model!r}: 'fundamental' or 'homography'")
+    if model in ("essential", "E", KIND_E):
+        return KIND_E
+    raise ValueError(f"unknown model {model!r}: 'fundamental', 'homography' or 'essential'")
 
 
 def _points(x_A, x_B, kind):
@@ -67,11 +74,18 @@ def _args(threshold, max_iters, lo_iters):
 
 
 def workspace_layout(kind, P, N, iters):
-    """(total bytes, [9 region offsets]) of the workspace (include/roma_hip.h, roma_ransac_workspace)."""
-    off = (ctypes.c_long * 9)()
-    total = _lib.load().roma_ransac_workspace(kind, P, N, iters, ctypes.cast(off, ctypes.c_void_p))
+    """(total bytes, [region offsets]) of the workspace (include/roma_hip.h: the 9 regions of roma_ransac_workspace, the 10 of
+    roma_essential_workspace for KIND_E)."""
+    if kind == KIND_E:
+        off = (ctypes.c_long * 10)()
+        total = _lib.load().roma_essential_workspace(P, N, iters, ctypes.cast(off, ctypes.c_void_p))
+        what = "roma_essential_workspace"
+    else:
+        off = (ctypes.c_long * 9)()
+        total = _lib.load().roma_ransac_workspace(kind, P, N, iters, ctypes.cast(off, ctypes.c_void_p))
+        what = "roma_ransac_workspace"
     if total < 0:
-        check(int(total), "roma_ransac_workspace")
+        check(int(total), what)
     return int(total), list(off)
 
 
@@ -84,16 +98,47 @@ def _chunks(kind, P, N, iters):
     return [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
 
 
-def _hypotheses(xa, xb, kind, threshold, iters, seed, p0, ws):
+def _intrinsics(K, P, device, name):
+    """(3,3) (shared by the batch) or (P,3,3), tensor or numpy -> contiguous (P,3,3) fp64 on the device."""
+    if not torch.is_tensor(K):
+        K = torch.as_tensor(K, dtype=torch.float64).to(device)
+    _need_gpu(K)
+    if K.shape not in ((3, 3), (P, 3, 3)):
+        raise ValueError(f"{name}: expected (3,3) or ({P},3,3) intrinsics, got {tuple(K.shape)}")
+    return K.to(torch.float64).expand(P, 3, 3).contiguous()
+
+
+def _inverse_intrinsics(K):
+    """K^-1 of upper-triangular K (..., 3, 3) with last row 0 0 1, in closed form as the kernels do (no host synchronisation; inf / NaN
+    for a singular K)."""
+    fx, s, cx, fy, cy = K[..., 0, 0], K[..., 0, 1], K[..., 0, 2], K[..., 1, 1], K[..., 1, 2]
+    T = torch.zeros_like(K)
+    T[..., 0, 0] = 1.0 / fx
+    T[..., 0, 1] = -s / (fx * fy)
+    T[..., 0, 2] = (s * cy - cx * fy) / (fx * fy)
+    T[..., 1, 1] = 1.0 / fy
+    T[..., 1, 2] = -cy / fy
+    T[..., 2, 2] = 1.0
+    return T
+
+
+def _hypotheses(xa, xb, kind, threshold, iters, seed, p0, ws, K=None):
     P, N = xa.shape[0], xa.shape[1]
+    if kind == KIND_E:
+        check(_lib.load().roma_essential_hypotheses(xa.data_ptr(), xb.data_ptr(), K[0].data_ptr(), K[1].data_ptr(), P, N, iters,
+                                                    float(threshold), seed, p0, ws.data_ptr(), ws.numel(), _stream()),
+              "roma_essential_hypotheses")
+        return
     check(_lib.load().roma_ransac_hypotheses(kind, xa.data_ptr(), xb.data_ptr(), P, N, iters, float(threshold), seed, p0,
                                              ws.data_ptr(), ws.numel(), _stream()), "roma_ransac_hypotheses")
 
 
-def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters):
+def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_B=None):
     _args(threshold, max_iters, lo_iters)
     xa, xb, single = _points(x_A, x_B, kind)
     P, N = xa.shape[0], xa.shape[1]
+    if kind == KIND_E:
+        Ka, Kb = _intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")
     iters, seed = int(max_iters), _seed(seed)
     model = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
     mask = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
@@ -104,6 +149,12 @@ def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters):
     ws = torch.empty((total,), dtype=torch.uint8, device=xa.device)
     for a, b in chunks:
         ca, cb = xa[a:b], xb[a:b]
+        if kind == KIND_E:
+            _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws, (Ka[a:b], Kb[a:b]))
+            check(lib.roma_essential_select(ca.data_ptr(), cb.data_ptr(), Ka[a:b].data_ptr(), Kb[a:b].data_ptr(), b - a, N, iters,
+                                            float(threshold), int(lo_iters), ws.data_ptr(), total, model[a:b].data_ptr(),
+                                            mask[a:b].data_ptr(), _stream()), "roma_essential_select")
+            continue
         _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws)
         check(lib.roma_ransac_select(kind, ca.data_ptr(), cb.data_ptr(), b - a, N, iters, float(threshold), int(lo_iters),
                                      ws.data_ptr(), total, model[a:b].data_ptr(), mask[a:b].data_ptr(), _stream()),
@@ -125,6 +176,71 @@ def find_homography(x_A, x_B, threshold=3.0, max_iters=2000, seed=None, lo_iters
     return _estimate(x_A, x_B, KIND_H, threshold, max_iters, seed, lo_iters)
 
 
+def find_essential(x_A, x_B, K_A, K_B, threshold, max_iters=2000, seed=None, lo_iters=3):
+    """Essential matrix E (x_hat_B^T E x_hat_A = 0, x_hat = K^-1 x) of PIXEL correspondences x_A <-> x_B, (N,2) or (P,N,2), fp32/fp64 on
+    the device; K_A, K_B: (3,3) (shared by the batch) or (P,3,3) intrinsics, tensors or numpy, upper triangular with last row 0 0 1.
+    threshold is in calibrated units (the reference's norm_thresh, e.g. 0.5 px / focal length): inlier when the Sampson error of the
+    calibrated points is below it.  Returns (E fp64 (3,3) or (P,3,3) with singular values (1, 1, 0) / sqrt 2 and its largest-magnitude
+    entry positive; inlier mask bool).  All zeros and an empty mask when no sample gives a model, e.g. for a singular K.
+    max_iters = 2000 samples of 5 points, up to 10 models each, every one scored: there is no confidence exit, so the number of
+    samples is the whole budget.  At 30 % inliers (1 - 0.3^5)^2000 = 0.8 % of the calls draw no clean sample, at 40 % 1e-9; raise
+    max_iters for harder pairs."""
+    return _estimate(x_A, x_B, KIND_E, threshold, max_iters, seed, lo_iters, K_A, K_B)
+
+
+def recover_pose(E, x_A, x_B, K_A, K_B, mask=None):
+    """Relative pose (R, t) of camera B with respect to A (X_B = R X_A + t, |t| = 1) from an essential matrix — of find_essential, or
+    K_B^T F K_A of find_fundamental — by the cheirality vote of cv2.recoverPose: of the four decompositions the one under which most
+    matches of `mask` (bool / uint8, default all) have positive depth in both cameras.  E (3,3) or (P,3,3); points and intrinsics as
+    find_essential.  Returns (R fp64 (3,3) / (P,3,3), t fp64 (3,) / (P,3), the mask narrowed to the matches that passed — what the
+    reference's estimate_pose returns).  A zero E gives R = I, t = 0 and an empty mask."""
+    _need_gpu(E)
+    xa, xb, single = _points(x_A, x_B, KIND_E)
+    P, N = xa.shape[0], xa.shape[1]
+    if E.shape != ((3, 3) if single else (P, 3, 3)):
+        raise ValueError(f"E {tuple(E.shape)} does not match the points {tuple(x_A.shape)}")
+    Ka, Kb = _intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")
+    e = E.reshape(P, 3, 3).to(torch.float64).contiguous()
+    m = None
+    if mask is not None:
+        _need_gpu(mask)
+        if mask.shape != ((N,) if single else (P, N)):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
+        m = mask.reshape(P, N).to(torch.uint8).contiguous()
+    R = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
+    t = torch.empty((P, 3), dtype=torch.float64, device=xa.device)
+    count = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    out = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
+    check(_lib.load().roma_recover_pose(xa.data_ptr(), xb.data_ptr(), Ka.data_ptr(), Kb.data_ptr(), e.data_ptr(),
+                                        None if m is None else m.data_ptr(), P, N, R.data_ptr(), t.data_ptr(), count.data_ptr(),
+                                        out.data_ptr(), _stream()), "roma_recover_pose")
+    out = out.bool()
+    return (R[0], t[0], out[0]) if single else (R, t, out)
+
+
+def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=2000, seed=None):
+    """Drop-in for estimate_pose of the reference (romatch/utils/utils.py:31-52) on the device: find_essential, then recover_pose on
+    its inliers.  None for fewer than 5 matches, else (R, t, mask) — batched tensors for (P,N,2) input.  `conf` is accepted for the
+    signature and unused: every one of the max_iters samples is drawn and scored, there is no early stop."""
+    if kpts0.shape[-2] < 5:
+        return None
+    E, mask = find_essential(kpts0, kpts1, K0, K1, norm_thresh, max_iters=max_iters, seed=seed)
+    return recover_pose(E, kpts0, kpts1, K0, K1, mask)
+
+
+def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=10000, seed=None):
+    """Drop-in for estimate_pose_uncalibrated of the reference (utils.py:54-76): find_fundamental with norm_thresh in PIXELS, E =
+    K1^T F K0, recover_pose on the inliers of F.  None for fewer than 5 matches (find_fundamental itself needs 7).  `conf` unused."""
+    if kpts0.shape[-2] < 5:
+        return None
+    F, mask = find_fundamental(kpts0, kpts1, threshold=norm_thresh, max_iters=max_iters, seed=seed)
+    P = 1 if F.dim() == 2 else F.shape[0]
+    Ka, Kb = _intrinsics(K0, P, F.device, "K0"), _intrinsics(K1, P, F.device, "K1")
+    if F.dim() == 2:
+        Ka, Kb = Ka[0], Kb[0]
+    return recover_pose(Kb.transpose(-1, -2) @ F @ Ka, kpts0, kpts1, Ka, Kb, mask)
+
+
 def _view(ws, off, i, dtype, shape):
     n = 1
     for s in shape:
@@ -133,20 +249,24 @@ def _view(ws, off, i, dtype, shape):
     return ws[off[i]:off[i] + n * item].view(dtype).reshape(shape)
 
 
-def minimal_samples(x_A, x_B, model="fundamental", max_iters=10000, seed=0):
-    """The indices each minimal sample draws: (P, max_iters, s) int32, s = 7 (F) / 4 (H), a row of -1 for an invalid sample.
-    An inspection helper like score_hypotheses, with its batch limit."""
-    return score_hypotheses(x_A, x_B, model, 3.0, max_iters, seed)["samples"]
+def minimal_samples(x_A, x_B, model="fundamental", max_iters=10000, seed=0, K_A=None, K_B=None):
+    """The indices each minimal sample draws: (P, max_iters, s) int32, s = 7 (F) / 4 (H) / 5 (E), a row of -1 for an invalid sample.
+    An inspection helper like score_hypotheses, with its batch limit.  model = "essential" takes the intrinsics (default: identity)."""
+    if _kind(model) == KIND_E and K_A is None and K_B is None:
+        K_A = K_B = torch.eye(3, dtype=torch.float64, device=x_A.device)
+    return score_hypotheses(x_A, x_B, model, 3.0, max_iters, seed, K_A, K_B)["samples"]
 
 
-def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=10000, seed=0):
+def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=10000, seed=0, K_A=None, K_B=None):
     """Every hypothesis of one call, before selection (batched (P,...) shapes even for a single pair):
     samples (P,iters,s) int32; models (P,iters,R,3,3) fp64 in normalised coordinates (unit Frobenius norm), R = 3 root slots
     for F, 1 for H; valid (P,iters,R) bool; count (P,iters,R) int32 inliers; cost (P,iters,R) fp64 MSAC cost (+inf if invalid);
     T_A, T_B (P,3,3) fp64 normalising transforms (x_hat = T x).  A model in pixels is T_B^T F^ T_A or T_B^-1 H^ T_A.
     Pair p draws what it draws in find_fundamental / find_homography with the same seed.  An inspection helper: it keeps the
     whole batch's workspace and returns every slot, so it refuses a batch whose workspace exceeds the chunk limit of the
-    estimators (192 MiB: about 35 pairs at N = 10 000 and 10 000 F samples) — call it on fewer pairs."""
+    estimators (192 MiB: about 35 pairs at N = 10 000 and 10 000 F samples) — call it on fewer pairs.
+    model = "essential" needs K_A, K_B (as find_essential; threshold in calibrated units): R = 10 slots ordered by the solver's
+    hidden variable, models in calibrated coordinates, T_A = K_A^-1, T_B = K_B^-1."""
     kind = _kind(model)
     _args(threshold, max_iters, 0)
     xa, xb, _ = _points(x_A, x_B, kind)
@@ -156,15 +276,22 @@ def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=100
         raise ValueError(f"score_hypotheses: {P} pairs need a {total >> 20} MiB workspace, over the {_WORKSPACE_LIMIT >> 20} MiB "
                          "limit; call it on fewer pairs")
     ws = torch.empty((total,), dtype=torch.uint8, device=xa.device)
-    _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws)
     S, R = _SMIN[kind], _SLOTS[kind]
-    norm = _view(ws, off, 0, torch.float64, (P, 2, 4))
-    T = torch.zeros((P, 2, 3, 3), dtype=torch.float64, device=xa.device)
-    T[:, :, 0, 0] = norm[:, :, 2]
-    T[:, :, 1, 1] = norm[:, :, 2]
-    T[:, :, 0, 2] = -norm[:, :, 2] * norm[:, :, 0]
-    T[:, :, 1, 2] = -norm[:, :, 2] * norm[:, :, 1]
-    T[:, :, 2, 2] = 1.0
+    if kind == KIND_E:
+        if K_A is None or K_B is None:
+            raise ValueError("score_hypotheses: model 'essential' needs K_A and K_B")
+        K = (_intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B"))
+        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, K)
+        T = _inverse_intrinsics(torch.stack(K, 1))
+    else:
+        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws)
+        norm = _view(ws, off, 0, torch.float64, (P, 2, 4))
+        T = torch.zeros((P, 2, 3, 3), dtype=torch.float64, device=xa.device)
+        T[:, :, 0, 0] = norm[:, :, 2]
+        T[:, :, 1, 1] = norm[:, :, 2]
+        T[:, :, 0, 2] = -norm[:, :, 2] * norm[:, :, 0]
+        T[:, :, 1, 2] = -norm[:, :, 2] * norm[:, :, 1]
+        T[:, :, 2, 2] = 1.0
     return {
         "samples": _view(ws, off, 2, torch.int32, (P, iters, S)).clone(),
         "models": _view(ws, off, 3, torch.float64, (P, iters, R, 3, 3)).clone(),

@@ -1,5 +1,7 @@
 # roma_amd.geometry call times with device events after warm-up: F at P = 1 (N = 10 000, 10 000 samples), F at P = 64 (N = 5 000,
-# MegaDepth-style), H at P = 1 (N = 5 000, 2 000 samples).  Model-point evaluations = P * samples * valid slots * N (the scoring work).
+# MegaDepth-style), H at P = 1 (N = 5 000, 2 000 samples), E (find_essential) and pose (estimate_pose = find_essential +
+# recover_pose) at P = 1 / N = 10 000 and P = 64 / N = 5 000 with 2 000 samples.  Model-point evaluations = P * samples * valid
+# slots * N (the scoring work).  `ransac_micro.py [reps] [kinds]`, e.g. `ransac_micro.py 3 E,pose` for a kernel trace of the E path.
 import os
 import sys
 
@@ -9,21 +11,36 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from roma_amd import geometry  # noqa: E402
 from tests import geometry_ref as G  # noqa: E402
+from tests import pose_ref as PR  # noqa: E402
 
-CASES = [("F", 1, 10000, 10000, 1.5), ("F", 64, 5000, 10000, 1.5), ("H", 1, 5000, 2000, 3.0)]
+CASES = [("F", 1, 10000, 10000, 1.5), ("F", 64, 5000, 10000, 1.5), ("H", 1, 5000, 2000, 3.0),
+         ("E", 1, 10000, 2000, 1.5 / 800), ("E", 64, 5000, 2000, 1.5 / 800), ("pose", 1, 10000, 2000, 1.5 / 800),
+         ("pose", 64, 5000, 2000, 1.5 / 800)]
+MODEL = {"F": "fundamental", "H": "homography", "E": "essential", "pose": "essential"}
 
 
 def scene(kind, P, N):
-    make = G.two_view_scene if kind == "F" else G.planar_scene
+    make = G.planar_scene if kind == "H" else G.two_view_scene
     pts = [make(100 + i, N=N)[:2] for i in range(P)]
     return (torch.from_numpy(np.stack([p[0] for p in pts])).float().cuda(), torch.from_numpy(np.stack([p[1] for p in pts])).float().cuda())
 
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    kinds = sys.argv[2].split(",") if len(sys.argv) > 2 else ["F", "H", "E", "pose"]
+    K = torch.from_numpy(PR.K_SCENE).cuda()
     for kind, P, N, iters, thr in CASES:
+        if kind not in kinds:
+            continue
         xa, xb = scene(kind, P, N)
-        fn = geometry.find_fundamental if kind == "F" else geometry.find_homography
+        if kind == "E":
+            def fn(a, b, threshold, max_iters, seed):
+                return geometry.find_essential(a, b, K, K, threshold, max_iters=max_iters, seed=seed)
+        elif kind == "pose":
+            def fn(a, b, threshold, max_iters, seed):
+                return geometry.estimate_pose(a, b, K, K, threshold, max_iters=max_iters, seed=seed)
+        else:
+            fn = geometry.find_fundamental if kind == "F" else geometry.find_homography
         for _ in range(3):
             fn(xa, xb, threshold=thr, max_iters=iters, seed=0)
         torch.cuda.synchronize()
@@ -36,11 +53,12 @@ def main():
             torch.cuda.synchronize()
             times.append(s.elapsed_time(e))
         # valid models at seed 0, counted on slices of 16 pairs (score_hypotheses keeps a whole batch's hypotheses)
-        valid = sum(int(geometry.score_hypotheses(xa[a:a + 16], xb[a:a + 16], "fundamental" if kind == "F" else "homography", thr,
-                                                  iters, seed=0)["valid"].sum()) for a in range(0, P, 16))
+        extra = {"K_A": K, "K_B": K} if MODEL[kind] == "essential" else {}
+        valid = sum(int(geometry.score_hypotheses(xa[a:a + 16], xb[a:a + 16], MODEL[kind], thr, iters, seed=0, **extra)["valid"].sum())
+                    for a in range(0, P, 16))
         evals = valid * N
         ms = float(np.median(times))
-        print(f"{kind} P={P:3d} N={N:5d} iters={iters:5d}: {ms:8.3f} ms/call (median of {reps}, min {min(times):.3f})  "
+        print(f"{kind:4s} P={P:3d} N={N:5d} iters={iters:5d}: {ms:8.3f} ms/call (median of {reps}, min {min(times):.3f})  "
               f"{ms / P:7.3f} ms/pair  {evals / (ms * 1e-3):.3e} model-point evaluations/s  ({evals:.3e} evaluations, "
               f"{valid} valid models)")
 
