@@ -337,6 +337,21 @@ int roma_recover_pose(const double* xa, const double* xb, const double* Ka, cons
                       const unsigned char* mask_in, int P, int N, double* R, double* t, int* count, unsigned char* mask_out,
                       void* stream);
 
+/* Non-linear refinement of a relative pose (csrc/pose_refine.hip) — the Levenberg-Marquardt stage behind the RANSAC
+ * of poselib.estimate_relative_pose, which the reference's PoseLib benchmark calls.  Points and intrinsics as roma_recover_pose
+ * (xa, xb 16-byte aligned); R_in (P,3,3), t_in (P,3): the pose to start from, e.g. of roma_recover_pose; mask_in: (P,N) uint8, the
+ * matches that may carry weight (NULL = all).  Minimises the sum over the usable matches of min(r^2, threshold^2), r the Sampson
+ * residual of x_hat = K^-1 x under E = [t]x R, threshold in calibrated units (fp64 here: the kernel compares fp64 residuals with
+ * it), by at most `iters` damped Gauss-Newton steps over 3 rotation and 2 translation-direction parameters.  A step is kept only if
+ * it lowers the cost, so the cost of the output is never above that of the input.
+ * R: (P,3,3) orthonormal, t: (P,3) unit; mask: (P,N) uint8, r^2 < threshold^2 under the returned pose; cost: (P) fp64 its cost;
+ * count: (P) int32 its inliers; steps: (P) int32 the steps kept.  A pair with fewer than 5 weighted matches, a singular normal
+ * matrix, or an input pose that is not finite or has t = 0 gets its input pose back unchanged (steps = 0).  Outputs must not
+ * overlap inputs.  One launch, no workspace, no host synchronisation; bitwise reproducible, and independent of the other pairs. */
+int roma_refine_pose(const double* xa, const double* xb, const double* Ka, const double* Kb, const double* R_in, const double* t_in,
+                     const unsigned char* mask_in, int P, int N, double threshold, int iters, double* R, double* t,
+                     unsigned char* mask, double* cost, int* count, int* steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

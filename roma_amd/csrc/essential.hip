@@ -49,15 +49,6 @@ constexpr int GROUP = 32, GROUPS = 8;                 // lanes per sample, sampl
 constexpr int BISECT_INNER = 32, BISECT_FINAL = 50, NEWTON_FINAL = 2, POLISH_ITERS = 3;
 constexpr uint32_t STAGE_E = 4u;
 
-// [fx s cx; 0 fy cy; 0 0 1]^-1 -> ki = (1/fx, -s/(fx fy), (s cy - cx fy)/(fx fy), 1/fy, -cy/fy); false when not invertible
-__device__ __forceinline__ bool invert_k(const double* K, double* ki) {
-  const double fx = K[0], s = K[1], cx = K[2], fy = K[4], cy = K[5];
-  const double d = fx * fy;
-  const bool ok = isfinite(fx) && isfinite(s) && isfinite(cx) && isfinite(fy) && isfinite(cy) && d != 0.0 && isfinite(1.0 / d);
-  ki[0] = 1.0 / fx; ki[1] = -s / d; ki[2] = (s * cy - cx * fy) / d; ki[3] = 1.0 / fy; ki[4] = -cy / fy;
-  return ok;
-}
-
 // xh: (P,N,4) fp64 calibrated (xa, ya, xb, yb); pts: the fp32 copy; norm: (0, 0, 1, 0) twice
 __global__ __launch_bounds__(256) void calibrate_kernel(const double* __restrict__ xa, const double* __restrict__ xb,
                                                         const double* __restrict__ Ka, const double* __restrict__ Kb, int N,

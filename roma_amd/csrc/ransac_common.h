@@ -35,6 +35,15 @@ __device__ __forceinline__ void unit_frobenius(double* m) {
   for (int i = 0; i < 9; ++i) m[i] *= inv;
 }
 
+// [fx s cx; 0 fy cy; 0 0 1]^-1 -> ki = (1/fx, -s/(fx fy), (s cy - cx fy)/(fx fy), 1/fy, -cy/fy); false when not invertible
+__device__ __forceinline__ bool invert_k(const double* K, double* ki) {
+  const double fx = K[0], s = K[1], cx = K[2], fy = K[4], cy = K[5];
+  const double d = fx * fy;
+  const bool ok = isfinite(fx) && isfinite(s) && isfinite(cx) && isfinite(fy) && isfinite(cy) && d != 0.0 && isfinite(1.0 / d);
+  ki[0] = 1.0 / fx; ki[1] = -s / d; ki[2] = (s * cy - cx * fy) / d; ki[3] = 1.0 / fy; ki[4] = -cy / fy;
+  return ok;
+}
+
 // Forward elimination with partial pivoting of the ROWS x 9 system, fully unrolled (rows are swapped by conditional selects, so
 // every index is a compile-time constant and A stays in registers).  Returns false when a pivot fails the relative tolerance.
 template <int ROWS> __device__ __forceinline__ bool eliminate(double (&A)[ROWS][9]) {

@@ -10,6 +10,11 @@ No host synchronisation: a call can be captured in a hipGraph.  Tensors must liv
 `find_essential`, `recover_pose`, `estimate_pose` and `estimate_pose_uncalibrated` are the calibrated counterpart (csrc/essential.hip):
 the 5-point solver on K^-1 x, the same scoring and selection, local optimisation on the essential manifold, and the cheirality
 vote of cv2.recoverPose — what the reference's pose benchmarks run per pair on the host (romatch/utils/utils.py:12-76).
+
+`refine_pose` polishes a pose by Levenberg-Marquardt on the truncated Sampson cost (csrc/pose_refine.hip), and
+`estimate_relative_pose` chains find_essential -> recover_pose -> refine_pose behind the signature of
+poselib.estimate_relative_pose, the call of the reference's PoseLib benchmark
+(romatch/benchmarks/megadepth_pose_estimation_benchmark_poselib.py:82-95).  `pose_error` is compute_pose_error on the device.
 """
 from __future__ import annotations
 
@@ -239,6 +244,146 @@ def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, 
     if F.dim() == 2:
         Ka, Kb = Ka[0], Kb[0]
     return recover_pose(Kb.transpose(-1, -2) @ F @ Ka, kpts0, kpts1, Ka, Kb, mask)
+
+
+def _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask):
+    """refine_pose on batched outputs: (R (P,3,3), t (P,3), mask (P,N) bool, cost (P,) fp64, count (P,) int32, steps (P,) int32), single"""
+    _need_gpu(R, t)
+    if not float(threshold) > 0:
+        raise ValueError(f"threshold must be positive, got {threshold}")
+    if int(iters) < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    xa, xb, single = _points(x_A, x_B, KIND_E)
+    P, N = xa.shape[0], xa.shape[1]
+    if R.shape != ((3, 3) if single else (P, 3, 3)) or t.shape != ((3,) if single else (P, 3)):
+        raise ValueError(f"R {tuple(R.shape)}, t {tuple(t.shape)} do not match the points {tuple(x_A.shape)}")
+    Ka, Kb = _intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")
+    r0 = R.reshape(P, 3, 3).to(torch.float64).contiguous()
+    t0 = t.reshape(P, 3).to(torch.float64).contiguous()
+    m = None
+    if mask is not None:
+        _need_gpu(mask)
+        if mask.shape != ((N,) if single else (P, N)):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
+        m = mask.reshape(P, N).to(torch.uint8).contiguous()
+    Ro = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
+    to = torch.empty((P, 3), dtype=torch.float64, device=xa.device)
+    out = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
+    cost = torch.empty((P,), dtype=torch.float64, device=xa.device)
+    count = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    steps = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    check(_lib.load().roma_refine_pose(xa.data_ptr(), xb.data_ptr(), Ka.data_ptr(), Kb.data_ptr(), r0.data_ptr(), t0.data_ptr(),
+                                       None if m is None else m.data_ptr(), P, N, float(threshold), int(iters), Ro.data_ptr(),
+                                       to.data_ptr(), out.data_ptr(), cost.data_ptr(), count.data_ptr(), steps.data_ptr(), _stream()),
+          "roma_refine_pose")
+    return (Ro, to, out.bool(), cost, count, steps), single
+
+
+def refine_pose(R, t, x_A, x_B, K_A, K_B, threshold, iters=15, mask=None, return_info=False):
+    """Non-linear refinement of a relative pose (R, t) — of recover_pose / estimate_pose — on the matches it was estimated from:
+    Levenberg-Marquardt, at most `iters` steps, on the sum over the matches of min(r^2, threshold^2), r the Sampson residual of the
+    calibrated points under E = [t]x R (threshold in calibrated units, as find_essential).  Matches beyond the threshold carry no
+    weight (the truncated loss, the MSAC score of the estimator), and `mask` (bool / uint8) optionally names the only matches that
+    may carry any.  R (3,3) or (P,3,3), t (3,) or (P,3); points and intrinsics as recover_pose.  Returns (R orthonormal fp64, t unit
+    fp64, mask bool: r^2 < threshold^2 under the returned pose); with return_info also a dict of device tensors: cost (fp64, the
+    truncated cost of the returned pose), count (int32, its inliers), steps (int32, the steps kept).  A step is kept only if it
+    lowers the cost, so the returned pose never has a higher cost than the given one; a pair that cannot be refined (fewer than 5
+    weighted matches, a singular normal matrix, a pose that is not finite) gets its pose back unchanged."""
+    (Ro, to, out, cost, count, steps), single = _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask)
+    res = (Ro[0], to[0], out[0]) if single else (Ro, to, out)
+    if not return_info:
+        return res
+    info = {"cost": cost, "count": count, "steps": steps}
+    return res + ({k: v[0] for k, v in info.items()} if single else info,)
+
+
+class RelativePose:
+    """What estimate_relative_pose returns in place of poselib.CameraPose: R (3,3) / (P,3,3), t (3,) / (P,3) (unit), Rt = [R | t]
+    (3,4) / (P,3,4), fp64 device tensors."""
+    __slots__ = ("R", "t")
+
+    def __init__(self, R, t):
+        self.R, self.t = R, t
+
+    @property
+    def Rt(self):
+        return torch.cat([self.R, self.t.unsqueeze(-1)], -1)
+
+    def __repr__(self):
+        return f"RelativePose(R={tuple(self.R.shape)}, t={tuple(self.t.shape)}, device={self.R.device})"
+
+
+_RANSAC_OPT = {"max_epipolar_error": 1.0, "max_iterations": 2000, "min_inliers": 5, "refine_iterations": 15, "max_reproj_error": None}
+
+
+def _focal(camera, name):
+    if not isinstance(camera, dict) or camera.get("model") != "PINHOLE":
+        model = camera.get("model") if isinstance(camera, dict) else type(camera).__name__
+        raise ValueError(f"{name}: camera model {model!r} is not supported, only 'PINHOLE' with params = [fx, fy, cx, cy]")
+    params = [float(v) for v in camera["params"]]
+    if len(params) != 4:
+        raise ValueError(f"{name}: a PINHOLE camera has 4 params [fx, fy, cx, cy], got {len(params)}")
+    fx, fy, cx, cy = params
+    return 0.5 * (fx + fy), [[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]]
+
+
+def estimate_relative_pose(kpts0, kpts1, camera0, camera1, ransac_opt=None, *, seed=None):
+    """Drop-in for poselib.estimate_relative_pose as the reference's PoseLib benchmark calls it, on the device: find_essential ->
+    recover_pose -> refine_pose (RANSAC, cheirality, then Levenberg-Marquardt on the truncated Sampson cost of all matches).
+    kpts0, kpts1: (N,2) or (P,N,2) pixel coordinates on the device; camera0, camera1: dicts with model 'PINHOLE' and params
+    [fx, fy, cx, cy] (one camera per image for the whole batch).  ransac_opt keys:
+      max_epipolar_error  pixels, default 1.0.  OUR DEFINITION of the calibrated threshold: max_epipolar_error * (1/f0 + 1/f1) / 2
+                          with f = (fx + fy) / 2 of each camera
+      max_iterations      default 2000 samples, not PoseLib's 10 000: there is no early exit here, every sample is drawn and
+                          scored, so this is the whole budget and not a cap (see find_essential for what 2000 buys)
+      min_inliers         default 5: a pair whose RANSAC pose has fewer inliers that pass cheirality keeps that pose unrefined
+      refine_iterations   default 15 Levenberg-Marquardt steps
+      max_reproj_error    accepted (the reference passes it) and unused: it belongs to PoseLib's absolute-pose estimators
+    Any other key, or another camera model, raises ValueError.  Returns (pose, info): pose.R, pose.t, pose.Rt; info = {inliers: bool
+    mask of the returned pose, num_inliers: int32, model_score: fp64 truncated cost, refinements: int32 steps kept — device tensors,
+    nothing is copied to the host —, iterations: max_iterations}."""
+    opt = dict(_RANSAC_OPT)
+    for k, v in (ransac_opt or {}).items():
+        if k not in opt:
+            raise ValueError(f"ransac_opt: unknown key {k!r}; known: {sorted(opt)}")
+        opt[k] = v
+    f0, K0 = _focal(camera0, "camera0")
+    f1, K1 = _focal(camera1, "camera1")
+    if not float(opt["max_epipolar_error"]) > 0:
+        raise ValueError(f"ransac_opt: max_epipolar_error must be positive, got {opt['max_epipolar_error']}")
+    if int(opt["max_iterations"]) < 1 or int(opt["min_inliers"]) < 0 or int(opt["refine_iterations"]) < 0:
+        raise ValueError(f"ransac_opt: bad counts {opt}")
+    _need_gpu(kpts0, kpts1)
+    thr = float(opt["max_epipolar_error"]) * 0.5 * (1.0 / f0 + 1.0 / f1)
+    K0 = torch.tensor(K0, dtype=torch.float64).to(kpts0.device)
+    K1 = torch.tensor(K1, dtype=torch.float64).to(kpts0.device)
+    E, emask = find_essential(kpts0, kpts1, K0, K1, thr, max_iters=int(opt["max_iterations"]), seed=seed)
+    R0, t0, mask0 = recover_pose(E, kpts0, kpts1, K0, K1, emask)
+    (R, t, mask, cost, count, steps), single = _refine(R0, t0, kpts0, kpts1, K0, K1, thr, int(opt["refine_iterations"]), None)
+    if single:
+        R, t, mask, cost, count, steps = R[0], t[0], mask[0], cost[0], count[0], steps[0]
+    keep = mask0.sum(-1) >= int(opt["min_inliers"])                  # on the device: no host synchronisation
+    R = torch.where(keep[..., None, None], R, R0)
+    t = torch.where(keep[..., None], t, t0)
+    steps = torch.where(keep, steps, torch.zeros_like(steps))
+    info = {"inliers": mask, "num_inliers": count, "model_score": cost, "iterations": int(opt["max_iterations"]), "refinements": steps}
+    return RelativePose(R, t), info
+
+
+def pose_error(R, t, T_gt):
+    """compute_pose_error of the reference (romatch/utils/utils.py:116-134) in torch on the device, batched, so that a benchmark loop
+    needs no copy to the host before its AUC: R (...,3,3), t (...,3) against T_gt (...,3,4) or (...,4,4) = [R_gt | t_gt] (tensor or
+    numpy).  Returns (e_t, e_R) in degrees: the angle between the translation directions folded by the sign ambiguity of E,
+    min(e, 180 - e), and the geodesic angle of R^T R_gt."""
+    _need_gpu(R, t)
+    T_gt = torch.as_tensor(T_gt).to(device=R.device, dtype=R.dtype)
+    R_gt, t_gt = T_gt[..., :3, :3], T_gt[..., :3, 3]
+    n = torch.linalg.norm(t, dim=-1) * torch.linalg.norm(t_gt, dim=-1)
+    e_t = torch.rad2deg(torch.acos(torch.clamp((t * t_gt).sum(-1) / n, -1.0, 1.0)))
+    e_t = torch.minimum(e_t, 180.0 - e_t)
+    cos = ((R * R_gt).sum((-1, -2)) - 1.0) / 2.0                    # trace(R^T R_gt) = sum of the elementwise product
+    e_R = torch.rad2deg(torch.acos(torch.clamp(cos, -1.0, 1.0)).abs())
+    return e_t, e_R
 
 
 def _view(ws, off, i, dtype, shape):

@@ -2,6 +2,8 @@
 # MegaDepth-style), H at P = 1 (N = 5 000, 2 000 samples), E (find_essential) and pose (estimate_pose = find_essential +
 # recover_pose) at P = 1 / N = 10 000 and P = 64 / N = 5 000 with 2 000 samples.  Model-point evaluations = P * samples * valid
 # slots * N (the scoring work).  `ransac_micro.py [reps] [kinds]`, e.g. `ransac_micro.py 3 E,pose` for a kernel trace of the E path.
+# refine = refine_pose alone from the pose of estimate_pose (seed 0), relpose = estimate_relative_pose (find_essential +
+# recover_pose + refine_pose), at the two pose shapes; their lines give the kept steps instead of model-point evaluations.
 import os
 import sys
 
@@ -15,8 +17,10 @@ from tests import pose_ref as PR  # noqa: E402
 
 CASES = [("F", 1, 10000, 10000, 1.5), ("F", 64, 5000, 10000, 1.5), ("H", 1, 5000, 2000, 3.0),
          ("E", 1, 10000, 2000, 1.5 / 800), ("E", 64, 5000, 2000, 1.5 / 800), ("pose", 1, 10000, 2000, 1.5 / 800),
-         ("pose", 64, 5000, 2000, 1.5 / 800)]
+         ("pose", 64, 5000, 2000, 1.5 / 800), ("refine", 1, 10000, 2000, 1.5 / 800), ("refine", 64, 5000, 2000, 1.5 / 800),
+         ("relpose", 1, 10000, 2000, 1.5 / 800), ("relpose", 64, 5000, 2000, 1.5 / 800)]
 MODEL = {"F": "fundamental", "H": "homography", "E": "essential", "pose": "essential"}
+CAMERA = {"model": "PINHOLE", "params": [800.0, 800.0, G.W_IMG / 2, G.H_IMG / 2]}
 
 
 def scene(kind, P, N):
@@ -27,7 +31,7 @@ def scene(kind, P, N):
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-    kinds = sys.argv[2].split(",") if len(sys.argv) > 2 else ["F", "H", "E", "pose"]
+    kinds = sys.argv[2].split(",") if len(sys.argv) > 2 else ["F", "H", "E", "pose", "refine", "relpose"]
     K = torch.from_numpy(PR.K_SCENE).cuda()
     for kind, P, N, iters, thr in CASES:
         if kind not in kinds:
@@ -39,6 +43,15 @@ def main():
         elif kind == "pose":
             def fn(a, b, threshold, max_iters, seed):
                 return geometry.estimate_pose(a, b, K, K, threshold, max_iters=max_iters, seed=seed)
+        elif kind == "refine":
+            R0, t0, _ = geometry.estimate_pose(xa, xb, K, K, thr, max_iters=iters, seed=0)
+
+            def fn(a, b, threshold, max_iters, seed):
+                return geometry.refine_pose(R0, t0, a, b, K, K, threshold, return_info=True)
+        elif kind == "relpose":
+            def fn(a, b, threshold, max_iters, seed):
+                return geometry.estimate_relative_pose(a, b, CAMERA, CAMERA, {"max_epipolar_error": threshold * 800,
+                                                                              "max_iterations": max_iters}, seed=seed)
         else:
             fn = geometry.find_fundamental if kind == "F" else geometry.find_homography
         for _ in range(3):
@@ -52,12 +65,18 @@ def main():
             e.record()
             torch.cuda.synchronize()
             times.append(s.elapsed_time(e))
+        ms = float(np.median(times))
+        if kind in ("refine", "relpose"):
+            out = fn(xa, xb, threshold=thr, max_iters=iters, seed=0)
+            steps = (out[3]["steps"] if kind == "refine" else out[1]["refinements"]).float()
+            print(f"{kind:7s} P={P:3d} N={N:5d} iters={iters:5d}: {ms:8.3f} ms/call (median of {reps}, min {min(times):.3f})  "
+                  f"{ms / P:7.3f} ms/pair  kept LM steps: mean {float(steps.mean()):.2f}, max {int(steps.max())} of 15")
+            continue
         # valid models at seed 0, counted on slices of 16 pairs (score_hypotheses keeps a whole batch's hypotheses)
         extra = {"K_A": K, "K_B": K} if MODEL[kind] == "essential" else {}
         valid = sum(int(geometry.score_hypotheses(xa[a:a + 16], xb[a:a + 16], MODEL[kind], thr, iters, seed=0, **extra)["valid"].sum())
                     for a in range(0, P, 16))
         evals = valid * N
-        ms = float(np.median(times))
         print(f"{kind:4s} P={P:3d} N={N:5d} iters={iters:5d}: {ms:8.3f} ms/call (median of {reps}, min {min(times):.3f})  "
               f"{ms / P:7.3f} ms/pair  {evals / (ms * 1e-3):.3e} model-point evaluations/s  ({evals:.3e} evaluations, "
               f"{valid} valid models)")
