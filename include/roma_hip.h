@@ -352,6 +352,21 @@ int roma_refine_pose(const double* xa, const double* xb, const double* Ka, const
                      const unsigned char* mask_in, int P, int N, double threshold, int iters, double* R, double* t,
                      unsigned char* mask, double* cost, int* count, int* steps, void* stream);
 
+/* Non-linear refinement of a fundamental matrix (csrc/fundamental_refine.hip) — the polish cv2.findFundamentalMat
+ * runs after consensus, behind roma_ransac_select(kind 0).  xa, xb: (P,N,2) fp64 pixels, 16-byte aligned; F_in: (P,3,3), the model
+ * to start from, any scale; mask_in: (P,N) uint8, the matches that may carry weight (NULL = all).  Minimises the sum over the usable
+ * matches of min(r^2, threshold^2), r the Sampson residual in pixels (threshold in pixels, fp64), by at most `iters` damped
+ * Gauss-Newton steps over the 7 parameters of F^ = U diag(1, s, 0) V^T in Hartley-normalised coordinates (the normalisation is
+ * computed in the kernel).  A step is kept only if it lowers the cost.
+ * F: (P,3,3), per pair EITHER a rank-2 model of unit Frobenius norm, largest-magnitude entry positive, of strictly lower cost than
+ * F_in (steps >= 1), OR F_in bit for bit (steps = 0): no step lowered the cost, fewer than 8 weighted matches under F_in, a singular
+ * normal matrix, an F_in that is not finite or has rank below 2.  mask: (P,N) uint8, r^2 < threshold^2 under the returned model;
+ * cost: (P) fp64 its cost; count: (P) int32 its inliers (= the sum of mask); steps: (P) int32 the steps kept.  Outputs must not
+ * overlap inputs.  One launch, no workspace, no host synchronisation; bitwise reproducible, and independent of the other pairs. */
+int roma_refine_fundamental(const double* xa, const double* xb, const double* F_in, const unsigned char* mask_in, int P, int N,
+                            double threshold, int iters, double* F, unsigned char* mask, double* cost, int* count, int* steps,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,7 @@ namespace {
 
 constexpr int RP_THREADS = 256, RP_WAVES = RP_THREADS / 64;
 constexpr int RP_NPAR = 5, RP_NSUM = 22;                      // 15 + 5 + cost + count
-constexpr int RP_MIN_MATCHES = 5, RP_EXP_TERMS = 10;
+constexpr int RP_MIN_MATCHES = 5;
 constexpr double RP_LAMBDA0 = 1e-3, RP_LAMBDA_MIN = 1e-10, RP_ACCEPT_REL = 1e-12;
 
 // out = [v]x A (3 x 3, row major)
@@ -45,12 +45,6 @@ __device__ __forceinline__ void skew_mul(const double* v, const double* A, doubl
     out[3 + c] = v[2] * A[c] - v[0] * A[6 + c];
     out[6 + c] = v[0] * A[3 + c] - v[1] * A[c];
   }
-}
-
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 __device__ __forceinline__ void tangent_basis(const double* t, double* b1, double* b2) {
@@ -78,28 +72,6 @@ __device__ __forceinline__ void model_matrices(const double* R, const double* t,
   }
   skew_mul(b1, R, M[4]);
   skew_mul(b2, R, M[5]);
-}
-
-// (m x_A)_{0,1,2} and (m^T x_B)_{0,1} for x_A = (x, y, 1), x_B = (u, v, 1); every operation is written out, so the passes that
-// use it agree bit for bit
-__device__ __forceinline__ void apply_model(const double* m, double x, double y, double u, double v, double* mx, double* mt) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) mx[r] = __builtin_fma(m[3 * r], x, __builtin_fma(m[3 * r + 1], y, m[3 * r + 2]));
-#pragma unroll
-  for (int c = 0; c < 2; ++c) mt[c] = __builtin_fma(m[c], u, __builtin_fma(m[3 + c], v, m[6 + c]));
-}
-
-// numerator n and denominator d of r = n / sqrt d
-__device__ __forceinline__ void sampson_terms(const double* ex, const double* et, double u, double v, double& n, double& d) {
-  n = __builtin_fma(u, ex[0], __builtin_fma(v, ex[1], ex[2]));
-  d = __builtin_fma(ex[0], ex[0], __builtin_fma(ex[1], ex[1], __builtin_fma(et[0], et[0], et[1] * et[1])));
-}
-
-// r^2 from n and d, the one expression every pass uses (NaN when d = 0 or the match is not finite: then it is no inlier)
-__device__ __forceinline__ double squared_residual(double n, double d, double& isd, double& r) {
-  isd = 1.0 / sqrt(d);
-  r = n * isd;
-  return r * r;
 }
 
 struct Match {
@@ -226,8 +198,7 @@ __device__ __forceinline__ bool solve_step(const double (&s)[RP_NSUM], double la
 
 // Rc = orthonormalised exp([w]x) R, tc = (t + a b1 + b b2) / |.|
 __device__ __forceinline__ void apply_step(const double* R, const double* t, const double (&delta)[RP_NPAR], double* Rc, double* tc) {
-  // A = sin(th) / th and B = (1 - cos(th)) / th^2 by their series in th^2, nested, 11 terms: exact to rounding for th <= 1, and
-  // the rotation of one step is limited to 1 rad (libm's sin would cost a spill of scalar registers)
+  // the rotation of one step is limited to 1 rad, where so3_exp_series is exact to rounding
   double w[3] = {delta[0], delta[1], delta[2]};
   double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
   if (th2 > 1.0) {
@@ -236,13 +207,8 @@ __device__ __forceinline__ void apply_step(const double* R, const double* t, con
     for (int i = 0; i < 3; ++i) w[i] *= sc;
     th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
   }
-  double A = 1.0, B = 1.0;
-#pragma unroll
-  for (int k = RP_EXP_TERMS - 1; k >= 0; --k) {
-    A = 1.0 - th2 * (1.0 / (double)((2 * k + 2) * (2 * k + 3))) * A;
-    B = 1.0 - th2 * (1.0 / (double)((2 * k + 3) * (2 * k + 4))) * B;
-  }
-  B *= 0.5;
+  double A, B;
+  so3_exp_series(th2, A, B, So3Literals());
   // exp([w]x) R = R + A [w]x R + B [w]x [w]x R
   double KR[9], KKR[9], X[9];
   skew_mul(w, R, KR);

@@ -1,6 +1,8 @@
 // What the RANSAC translation units share (geometry.hip: F / H, essential.hip: E): the counter-hash of the sample draw, the
 // fully unrolled fp64 elimination, fp32 MSAC scoring of every slot (score_kernel / reduce_kernel, no atomics), the block-wide
 // re-score and the LDS Jacobi of the select kernels.  geometry.hip's header pins the draw and the tolerances.  DESIGN.md §3.4.
+// Plus what the refinement kernels share (pose_refine.hip, fundamental_refine.hip): the Sampson residual written out in fused
+// multiply-adds and the series of exp([w]x).
 #pragma once
 #include "common.h"
 
@@ -42,6 +44,66 @@ __device__ __forceinline__ bool invert_k(const double* K, double* ki) {
   const bool ok = isfinite(fx) && isfinite(s) && isfinite(cx) && isfinite(fy) && isfinite(cy) && d != 0.0 && isfinite(1.0 / d);
   ki[0] = 1.0 / fx; ki[1] = -s / d; ki[2] = (s * cy - cx * fy) / d; ki[3] = 1.0 / fy; ki[4] = -cy / fy;
   return ok;
+}
+
+// ------------------------------------------------------------------ what the refinement kernels share (pose_refine, fundamental_refine)
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// (m x_A)_{0,1,2} and (m^T x_B)_{0,1} for x_A = (x, y, 1), x_B = (u, v, 1); every operation is written out, so the passes that
+// use it agree bit for bit
+__device__ __forceinline__ void apply_model(const double* m, double x, double y, double u, double v, double* mx, double* mt) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) mx[r] = __builtin_fma(m[3 * r], x, __builtin_fma(m[3 * r + 1], y, m[3 * r + 2]));
+#pragma unroll
+  for (int c = 0; c < 2; ++c) mt[c] = __builtin_fma(m[c], u, __builtin_fma(m[3 + c], v, m[6 + c]));
+}
+
+// numerator n and denominator d of the Sampson residual r = n / sqrt d
+__device__ __forceinline__ void sampson_terms(const double* ex, const double* et, double u, double v, double& n, double& d) {
+  n = __builtin_fma(u, ex[0], __builtin_fma(v, ex[1], ex[2]));
+  d = __builtin_fma(ex[0], ex[0], __builtin_fma(ex[1], ex[1], __builtin_fma(et[0], et[0], et[1] * et[1])));
+}
+
+// r^2 from n and d, the one expression every pass uses (NaN when d = 0 or the match is not finite: then it is no inlier)
+__device__ __forceinline__ double squared_residual(double n, double d, double& isd, double& r) {
+  isd = 1.0 / sqrt(d);
+  r = n * isd;
+  return r * r;
+}
+
+// exp([w]x) = I + A [w]x + B [w]x^2: A = sin(th) / th and B = (1 - cos(th)) / th^2 by their series in th2 = th^2, nested, 11 terms:
+// exact to rounding for th <= 1, which the callers ensure (libm's sin would cost a spill of scalar registers).  The 20 coefficients
+// come from `coef`: So3Literals (immediates, 38 scalar registers where the series sits in a loop) or So3Table (a table, e.g. in
+// LDS, that so3_fill_table wrote: the same 20 values)
+constexpr int SO3_EXP_TERMS = 10;
+constexpr double so3_coef_a(int k) { return 1.0 / (double)((2 * k + 2) * (2 * k + 3)); }
+constexpr double so3_coef_b(int k) { return 1.0 / (double)((2 * k + 3) * (2 * k + 4)); }
+struct So3Literals {
+  __device__ __forceinline__ double a(int k) const { return so3_coef_a(k); }
+  __device__ __forceinline__ double b(int k) const { return so3_coef_b(k); }
+};
+struct So3Table {
+  const double* t;                                              // 2 * SO3_EXP_TERMS values
+  __device__ __forceinline__ double a(int k) const { return t[k]; }
+  __device__ __forceinline__ double b(int k) const { return t[SO3_EXP_TERMS + k]; }
+};
+__device__ __forceinline__ void so3_fill_table(double* t) {
+#pragma unroll
+  for (int k = 0; k < SO3_EXP_TERMS; ++k) { t[k] = so3_coef_a(k); t[SO3_EXP_TERMS + k] = so3_coef_b(k); }
+}
+template <class Coef> __device__ __forceinline__ void so3_exp_series(double th2, double& A, double& B, const Coef& coef) {
+  A = 1.0;
+  B = 1.0;
+#pragma unroll
+  for (int k = SO3_EXP_TERMS - 1; k >= 0; --k) {
+    A = 1.0 - th2 * coef.a(k) * A;
+    B = 1.0 - th2 * coef.b(k) * B;
+  }
+  B *= 0.5;
 }
 
 // Forward elimination with partial pivoting of the ROWS x 9 system, fully unrolled (rows are swapped by conditional selects, so

@@ -15,6 +15,10 @@ vote of cv2.recoverPose — what the reference's pose benchmarks run per pair on
 `estimate_relative_pose` chains find_essential -> recover_pose -> refine_pose behind the signature of
 poselib.estimate_relative_pose, the call of the reference's PoseLib benchmark
 (romatch/benchmarks/megadepth_pose_estimation_benchmark_poselib.py:82-95).  `pose_error` is compute_pose_error on the device.
+
+`refine_fundamental` is the same polish for the uncalibrated path (csrc/fundamental_refine.hip): Levenberg-Marquardt on the truncated
+Sampson cost in pixels over the rank-2 manifold, what cv2.findFundamentalMat runs after consensus.  `find_fundamental` and
+`estimate_pose_uncalibrated` run it on request (refine_iters > 0).
 """
 from __future__ import annotations
 
@@ -168,11 +172,23 @@ def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_
     return (model[0], mask[0]) if single else (model, mask)
 
 
-def find_fundamental(x_A, x_B, threshold=3.0, max_iters=10000, seed=None, lo_iters=3):
+def _refine_iters(refine_iters):
+    if int(refine_iters) < 0:
+        raise ValueError(f"refine_iters must be >= 0, got {refine_iters}")
+    return int(refine_iters)
+
+
+def find_fundamental(x_A, x_B, threshold=3.0, max_iters=10000, seed=None, lo_iters=3, refine_iters=0):
     """Fundamental matrix F (x_B^T F x_A = 0) of pixel correspondences x_A <-> x_B, (N,2) or (P,N,2), fp32/fp64 on the device.
     Returns (F fp64 (3,3) or (P,3,3), unit Frobenius norm, largest-magnitude entry positive; inlier mask bool (N,) or (P,N)):
-    Sampson error below threshold (pixels).  All zeros and an empty mask when no sample gives a model."""
-    return _estimate(x_A, x_B, KIND_F, threshold, max_iters, seed, lo_iters)
+    Sampson error below threshold (pixels).  All zeros and an empty mask when no sample gives a model.
+    refine_iters > 0 polishes the RANSAC model by refine_fundamental on all matches at the same threshold (at most that many
+    Levenberg-Marquardt steps) and returns the refined model's mask; 0, the default, returns the RANSAC model as it is."""
+    refine_iters = _refine_iters(refine_iters)
+    F, mask = _estimate(x_A, x_B, KIND_F, threshold, max_iters, seed, lo_iters)
+    if refine_iters == 0:
+        return F, mask
+    return refine_fundamental(F, x_A, x_B, threshold, refine_iters)
 
 
 def find_homography(x_A, x_B, threshold=3.0, max_iters=2000, seed=None, lo_iters=3):
@@ -233,12 +249,14 @@ def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=
     return recover_pose(E, kpts0, kpts1, K0, K1, mask)
 
 
-def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=10000, seed=None):
+def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=10000, seed=None, refine_iters=0):
     """Drop-in for estimate_pose_uncalibrated of the reference (utils.py:54-76): find_fundamental with norm_thresh in PIXELS, E =
-    K1^T F K0, recover_pose on the inliers of F.  None for fewer than 5 matches (find_fundamental itself needs 7).  `conf` unused."""
+    K1^T F K0, recover_pose on the inliers of F.  None for fewer than 5 matches (find_fundamental itself needs 7).  `conf` unused.
+    refine_iters > 0: the pose comes from the F that refine_fundamental polished (see find_fundamental) and from its inliers."""
+    refine_iters = _refine_iters(refine_iters)
     if kpts0.shape[-2] < 5:
         return None
-    F, mask = find_fundamental(kpts0, kpts1, threshold=norm_thresh, max_iters=max_iters, seed=seed)
+    F, mask = find_fundamental(kpts0, kpts1, threshold=norm_thresh, max_iters=max_iters, seed=seed, refine_iters=refine_iters)
     P = 1 if F.dim() == 2 else F.shape[0]
     Ka, Kb = _intrinsics(K0, P, F.device, "K0"), _intrinsics(K1, P, F.device, "K1")
     if F.dim() == 2:
@@ -291,6 +309,50 @@ def refine_pose(R, t, x_A, x_B, K_A, K_B, threshold, iters=15, mask=None, return
     weighted matches, a singular normal matrix, a pose that is not finite) gets its pose back unchanged."""
     (Ro, to, out, cost, count, steps), single = _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask)
     res = (Ro[0], to[0], out[0]) if single else (Ro, to, out)
+    if not return_info:
+        return res
+    info = {"cost": cost, "count": count, "steps": steps}
+    return res + ({k: v[0] for k, v in info.items()} if single else info,)
+
+
+def refine_fundamental(F, x_A, x_B, threshold=3.0, iters=15, mask=None, return_info=False):
+    """Non-linear refinement of a fundamental matrix F — of find_fundamental — on the matches it was estimated from: Levenberg-
+    Marquardt, at most `iters` steps, on the sum over the matches of min(r^2, threshold^2), r the Sampson residual in pixels (what
+    find_fundamental scores with), over the rank-2 matrices (F^ = U diag(1, s, 0) V^T in normalised coordinates).  Matches beyond the
+    threshold carry no weight, and `mask` (bool / uint8) optionally names the only matches that may carry any.  F (3,3) or (P,3,3);
+    points as find_fundamental.  Returns (F fp64, mask bool: r^2 < threshold^2 under the returned model); with return_info also a
+    dict of device tensors: cost (fp64, the truncated cost of the returned model), count (int32, its inliers), steps (int32, the
+    steps kept).  A pair comes back either as a rank-2 model of unit Frobenius norm, largest-magnitude entry positive, of strictly
+    lower cost than the given F, or — no step lowered the cost, fewer than 8 weighted matches, a singular normal matrix, an F that is
+    not finite or has rank below 2 — as the given F bit for bit, with steps = 0."""
+    _need_gpu(F)
+    if not float(threshold) > 0:
+        raise ValueError(f"threshold must be positive, got {threshold}")
+    if int(iters) < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    xa, xb, single = _points(x_A, x_B, KIND_F)
+    P, N = xa.shape[0], xa.shape[1]
+    if N < 8:
+        raise ValueError(f"{N} matches, the refinement needs 8")
+    if F.shape != ((3, 3) if single else (P, 3, 3)):
+        raise ValueError(f"F {tuple(F.shape)} does not match the points {tuple(x_A.shape)}")
+    f0 = F.reshape(P, 3, 3).to(torch.float64).contiguous()
+    m = None
+    if mask is not None:
+        _need_gpu(mask)
+        if mask.shape != ((N,) if single else (P, N)):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
+        m = mask.reshape(P, N).to(torch.uint8).contiguous()
+    Fo = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
+    out = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
+    cost = torch.empty((P,), dtype=torch.float64, device=xa.device)
+    count = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    steps = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    check(_lib.load().roma_refine_fundamental(xa.data_ptr(), xb.data_ptr(), f0.data_ptr(), None if m is None else m.data_ptr(), P, N,
+                                              float(threshold), int(iters), Fo.data_ptr(), out.data_ptr(), cost.data_ptr(),
+                                              count.data_ptr(), steps.data_ptr(), _stream()), "roma_refine_fundamental")
+    out = out.bool()
+    res = (Fo[0], out[0]) if single else (Fo, out)
     if not return_info:
         return res
     info = {"cost": cost, "count": count, "steps": steps}

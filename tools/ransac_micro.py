@@ -4,6 +4,8 @@
 # slots * N (the scoring work).  `ransac_micro.py [reps] [kinds]`, e.g. `ransac_micro.py 3 E,pose` for a kernel trace of the E path.
 # refine = refine_pose alone from the pose of estimate_pose (seed 0), relpose = estimate_relative_pose (find_essential +
 # recover_pose + refine_pose), at the two pose shapes; their lines give the kept steps instead of model-point evaluations.
+# refineF = refine_fundamental alone from the model of find_fundamental (seed 0), Fref = find_fundamental(refine_iters=15), at the
+# two F shapes: the extra cost of the refinement inside the estimator is Fref minus F of the same run.
 import os
 import sys
 
@@ -18,8 +20,9 @@ from tests import pose_ref as PR  # noqa: E402
 CASES = [("F", 1, 10000, 10000, 1.5), ("F", 64, 5000, 10000, 1.5), ("H", 1, 5000, 2000, 3.0),
          ("E", 1, 10000, 2000, 1.5 / 800), ("E", 64, 5000, 2000, 1.5 / 800), ("pose", 1, 10000, 2000, 1.5 / 800),
          ("pose", 64, 5000, 2000, 1.5 / 800), ("refine", 1, 10000, 2000, 1.5 / 800), ("refine", 64, 5000, 2000, 1.5 / 800),
-         ("relpose", 1, 10000, 2000, 1.5 / 800), ("relpose", 64, 5000, 2000, 1.5 / 800)]
-MODEL = {"F": "fundamental", "H": "homography", "E": "essential", "pose": "essential"}
+         ("relpose", 1, 10000, 2000, 1.5 / 800), ("relpose", 64, 5000, 2000, 1.5 / 800),
+         ("refineF", 1, 10000, 10000, 1.5), ("refineF", 64, 5000, 10000, 1.5), ("Fref", 1, 10000, 10000, 1.5), ("Fref", 64, 5000, 10000, 1.5)]
+MODEL = {"F": "fundamental", "H": "homography", "E": "essential", "pose": "essential", "Fref": "fundamental"}
 CAMERA = {"model": "PINHOLE", "params": [800.0, 800.0, G.W_IMG / 2, G.H_IMG / 2]}
 
 
@@ -31,7 +34,7 @@ def scene(kind, P, N):
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-    kinds = sys.argv[2].split(",") if len(sys.argv) > 2 else ["F", "H", "E", "pose", "refine", "relpose"]
+    kinds = sys.argv[2].split(",") if len(sys.argv) > 2 else ["F", "H", "E", "pose", "refine", "relpose", "refineF", "Fref"]
     K = torch.from_numpy(PR.K_SCENE).cuda()
     for kind, P, N, iters, thr in CASES:
         if kind not in kinds:
@@ -52,6 +55,14 @@ def main():
             def fn(a, b, threshold, max_iters, seed):
                 return geometry.estimate_relative_pose(a, b, CAMERA, CAMERA, {"max_epipolar_error": threshold * 800,
                                                                               "max_iterations": max_iters}, seed=seed)
+        elif kind == "refineF":
+            F0, _ = geometry.find_fundamental(xa, xb, threshold=thr, max_iters=iters, seed=0)
+
+            def fn(a, b, threshold, max_iters, seed):
+                return geometry.refine_fundamental(F0, a, b, threshold, return_info=True)
+        elif kind == "Fref":
+            def fn(a, b, threshold, max_iters, seed):
+                return geometry.find_fundamental(a, b, threshold=threshold, max_iters=max_iters, seed=seed, refine_iters=15)
         else:
             fn = geometry.find_fundamental if kind == "F" else geometry.find_homography
         for _ in range(3):
@@ -66,9 +77,9 @@ def main():
             torch.cuda.synchronize()
             times.append(s.elapsed_time(e))
         ms = float(np.median(times))
-        if kind in ("refine", "relpose"):
+        if kind in ("refine", "relpose", "refineF"):
             out = fn(xa, xb, threshold=thr, max_iters=iters, seed=0)
-            steps = (out[3]["steps"] if kind == "refine" else out[1]["refinements"]).float()
+            steps = (out[1]["refinements"] if kind == "relpose" else out[-1]["steps"]).float()
             print(f"{kind:7s} P={P:3d} N={N:5d} iters={iters:5d}: {ms:8.3f} ms/call (median of {reps}, min {min(times):.3f})  "
                   f"{ms / P:7.3f} ms/pair  kept LM steps: mean {float(steps.mean()):.2f}, max {int(steps.max())} of 15")
             continue
