@@ -13,7 +13,6 @@
 //     32 ks + 8 kq .. +8 of pixel m), so the 1x1 conv runs on the matrix cores straight out of registers;
 //   * results go through LDS for 16-byte coalesced stores.
 #include <algorithm>
-#include <cstdlib>
 #include "common.h"
 #include "lc_device.h"
 
@@ -45,11 +44,7 @@ struct RBParams {
 
 constexpr int XT = 16, YT = 8, HX = XT + 4, HY = YT + 4, NPOS = HX * HY;
 
-// PKC: the real 16-byte packets per pixel as a compile-time constant (0: run-time p.C / 8).  The tile staging and the store loop turn
-// a linear index into (position, packet) and (row, column) for every 16-byte access; with a run-time divisor each of those is a ~35-
-// instruction sequence, and at D = 24 (PKC = 3, the two finest refiners, 18 launches per match) those divisions were as many
-// instructions as the 400 multiply-adds of a tile.
-template <typename T, int KP, int PKC>
+template <typename T, int KP>
 __global__ __launch_bounds__(256, 1) void refiner_block_kernel(RBParams p) {
   constexpr int KPAD = 32 * KP;            // padded channel count (inputs of the 1x1)
   constexpr int NT = KPAD / 16;            // 16-wide output tiles (outputs are padded to KPAD as well)
@@ -64,7 +59,7 @@ __global__ __launch_bounds__(256, 1) void refiner_block_kernel(RBParams p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int m = lane & 15, kq = lane >> 4;
-  const int PKT = PKC ? PKC : p.C / 8;                          // real packets per pixel
+  const int PKT = p.C / 8;                                      // real packets per pixel
   const T* x = static_cast<const T*>(p.x);
   T* y = static_cast<T*>(p.y);
   const int tiles_per_img = p.tiles_x * p.tiles_y;
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(256, 1) void refiner_block_kernel(RBParams p) {
   }
   // channel padding of the input tile (packets PKT .. KPAD/8-1) stays zero for the whole kernel
   const int ntile = p.tiles_x * p.tiles_y * p.B;
-  constexpr int NLD = (NPOS * (PKC ? PKC : KPAD / 8) + 255) / 256;   // 16-byte loads per thread and tile (upper bound)
+  constexpr int NLD = (NPOS * (KPAD / 8) + 255) / 256;          // 16-byte loads per thread and tile (upper bound)
   const int nload = NPOS * PKT;
   u32x4 pre[NLD];
   // The next tile's input is fetched into registers while the current one is computed (one workgroup per CU at
@@ -204,33 +199,20 @@ __global__ __launch_bounds__(256, 1) void refiner_block_kernel(RBParams p) {
   }
 }
 
-template <typename T, int KP, int PKC>
+template <typename T, int KP>
 int launch_rb(RBParams p, hipStream_t s) {
   constexpr int KPAD = 32 * KP, RS = KPAD / 8 + 1;
   const size_t smem = (size_t)(NPOS * RS + KPAD * RS + 25 * (KPAD / 8)) * 16 + 3 * KPAD * 4;
   static std::atomic<uint64_t> attr_done{0};
-  if (int rc = ensure_dyn_smem(reinterpret_cast<const void*>(refiner_block_kernel<T, KP, PKC>), (int)smem, attr_done, "roma_refiner_block")) return rc;
+  if (int rc = ensure_dyn_smem(reinterpret_cast<const void*>(refiner_block_kernel<T, KP>), (int)smem, attr_done, "roma_refiner_block")) return rc;
   const long ntile = (long)p.B * p.tiles_x * p.tiles_y;
   ROMA_REQUIRE(ntile < (1 << 21), ROMA_E_SHAPE, "roma_refiner_block: %ld tiles in one launch (< 2^21)", ntile);
   p.inv_tiles_per_img = 1.0f / (float)(p.tiles_x * p.tiles_y);
   p.inv_tiles_x = 1.0f / (float)p.tiles_x;
   const int per_cu = KP == 1 ? 4 : 1;                          // LDS footprint: ~25 KB (KP=1) or ~140 KB (KP=5)
   const int grid = ntile < 256 * per_cu ? (int)ntile : 256 * per_cu;
-  hipLaunchKernelGGL((refiner_block_kernel<T, KP, PKC>), dim3(grid), dim3(256), smem, s, p);
+  hipLaunchKernelGGL((refiner_block_kernel<T, KP>), dim3(grid), dim3(256), smem, s, p);
   ROMA_CHECK_LAUNCH();
-}
-
-template <typename T> int launch_rb_toep(RBParams p, hipStream_t s);   // the D = 24 block with the depthwise on the matrix cores (below)
-
-template <typename T>
-int launch_rb_any(const RBParams& p, int kpad, hipStream_t s) {
-  if (kpad == 32 && p.C == 24) {
-    static int toep = -1;                                          // ROMA_RB_TOEP=0: the VALU depthwise (A/B aid)
-    if (toep < 0) { const char* e = getenv("ROMA_RB_TOEP"); toep = e ? atoi(e) : 1; }
-    if (toep) return launch_rb_toep<T>(p, s);
-  }
-  if (kpad == 32) return p.C == 24 ? launch_rb<T, 1, 3>(p, s) : launch_rb<T, 1, 0>(p, s);
-  return launch_rb<T, 5, 0>(p, s);
 }
 
 
@@ -471,6 +453,12 @@ int launch_rb_toep(RBParams p, hipStream_t s) {
   const int grid = ntile < 2 * num_cus() ? (int)ntile : 2 * num_cus();      // persistent, two workgroups per CU
   hipLaunchKernelGGL((refiner_block_toep_kernel<T>), dim3(grid), dim3(256), TP_SMEM, s, p);
   ROMA_CHECK_LAUNCH();
+}
+
+template <typename T>
+int launch_rb_any(const RBParams& p, int kpad, hipStream_t s) {
+  if (kpad == 32 && p.C == 24) return launch_rb_toep<T>(p, s);
+  return kpad == 32 ? launch_rb<T, 1>(p, s) : launch_rb<T, 5>(p, s);
 }
 
 

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 from typing import Dict, Optional
 from warnings import warn
 
@@ -25,10 +26,6 @@ from .transformer import Block, TransformerDecoder  # noqa: F401  (re-exported l
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
-
-
-def _round_up(n, m):
-    return (n + m - 1) // m * m
 
 
 def pixel_grid(b, h, w, device):
@@ -51,12 +48,44 @@ def _zero_pad(t, *shape):
     return out
 
 
+# One block's prepared weights, named by the layout its kernels take (w25: depthwise taps, (25, C) tap-major; scale / shift: folded BN)
+BlockInOut = namedtuple("BlockInOut", "w25 scale shift wt_in_out bias")   # split_small (fp32 1x1 weight), split_gemm: rows @ wt_in_out
+BlockOutIn = namedtuple("BlockOutIn", "w25 scale shift wt_out_in bias")   # fused (all padded to 32 channels), split_mfma (1x1 padded to 160)
+BlockWide = namedtuple("BlockWide", "taps scale shift wt_panels bias")    # wide: the layouts of ops.refiner_wide_taps / refiner_wide_pack
+RefinerPlan = namedtuple("RefinerPlan", "D Dp blocks wo bo we be")        # blocks: {implementation: [one record per block]}
+
+
+def padded_width(D):
+    """Channel pitch Dp of a refiner of width D: 16-byte packets; the wide refiners (D = 1144, 1384) are padded to a multiple of 64
+    because hipBLASLt runs their square 1x1-conv GEMMs 23-34 % faster at K = N = 1152 / 1408 (576 already is a multiple of 64)."""
+    m = 64 if D > 160 else 8
+    return (D + m - 1) // m * m
+
+
+def block_impl(Dp, dtype, B, h, w):
+    """Which implementation runs the blocks of a refiner of padded width Dp on a (B,h,w) map — the table in ConvRefiner's docstring."""
+    half = dtype in (torch.float16, torch.bfloat16)
+    # wide: 160 vs 177 us per block at 216^2 x 2, but 97 vs 80 us at 140^2 x 2 (324 tiles of 128 pixels on 256 CUs: one and a quarter
+    # rounds) -> only when the map fills the chip twice
+    if dtype == torch.float16 and Dp == 576 and B * ((h + 7) // 8) * ((w + 15) // 16) >= 2 * 256:
+        return "wide"
+    if half and Dp <= 32:
+        return "fused"
+    if half and Dp <= 160:
+        return "split_mfma"
+    return "split_small" if Dp <= 32 else "split_gemm"
+
+
 class ConvRefiner(nn.Module):
-    """x, warped y, displacement embedding and local correlation are assembled in ONE channels-last buffer (pitch padded to
-    8 channels): the decoder's projection GEMM writes x there, three kernels write the other channel slices.  A block
-    (depthwise 5x5 + BN + ReLU + 1x1) is, by width: D <= 32 one fused kernel (ops.refiner_block); 32 < D <= 160 the
-    depthwise kernel + the streaming MFMA 1x1 (ops.pointwise_mfma); wider, the depthwise kernel + a hipBLASLt GEMM.  fp32
-    (parity mode) always takes the separate kernels."""
+    """x, warped y, displacement embedding and local correlation are assembled in ONE channels-last buffer (pitch Dp: D padded to
+    8 channels, to 64 above 160): the decoder's projection GEMM writes x there, three kernels write the other channel slices.  A
+    block (depthwise 5x5 + BN + ReLU + 1x1) is run by the first row that applies (block_impl):
+        fp16, Dp == 576, B*ceil(h/8)*ceil(w/16) >= 512   wide         ops.refiner_block_wide, one kernel
+        fp16/bf16, Dp <= 32                              fused        ops.refiner_block (kpad 32), one kernel
+        fp16/bf16, 32 < Dp <= 160                        split_mfma   ops.dwconv5x5_bn_relu + ops.pointwise_mfma (kpad 160)
+        fp32, Dp <= 32                                   split_small  ops.dwconv5x5_bn_relu + ops.pointwise_small (fp32 weights)
+        everything else                                  split_gemm   ops.dwconv5x5_bn_relu + a hipBLASLt GEMM (torch.addmm)
+    Measured (`refiner_block_kernel`): fused is 1.8x faster than split at D = 24, 209 vs 121 us at D = 144 (LDS-read bound)."""
 
     def __init__(self, in_dim, hidden_dim, out_dim, hidden_blocks, displacement_emb_dim, local_corr_radius=None,
                  amp_dtype=torch.float16):
@@ -81,20 +110,10 @@ class ConvRefiner(nn.Module):
         if self._prep is not None and self._prep[0] == key:
             return self._prep[1]
         D = self.in_dim
-        # channel pitch: 16-byte packets; the wide refiners (D = 1144, 1384) are padded to a multiple of 64 because hipBLASLt runs
-        # their square 1x1-conv GEMMs 23-34 % faster at K = N = 1152 / 1408 (576 already is a multiple of 64)
-        Dp = _round_up(D, 64) if D > 160 else _round_up(D, 8)
+        Dp = padded_width(D)
         dev = self.out_conv.weight.device
-        # whole-block fusion (ops.refiner_block): measured 1.8x faster than dwconv + pointwise at D = 24, on par at D = 144
-        # (LDS-read and VALU bound there) -> narrow refiners only unless ROMA_FUSED_BLOCK=160
-        fuse_max = int(os.environ.get("ROMA_FUSED_BLOCK", "32"))
-        fused = Dp <= min(fuse_max, 160) and dtype in (torch.float16, torch.bfloat16)
-        mid = (not fused) and 32 < Dp <= 160 and dtype in (torch.float16, torch.bfloat16) and os.environ.get("ROMA_PW_MFMA", "1") != "0"
-        # D = 576 (the scale-4 refiner), fp16: the whole block as one kernel (ops.refiner_block_wide, csrc/refiner_wide.hip) — prepared
-        # here, used per call when the map fills the chip (see _body): 160 vs 177 us per block at 216^2 x 2, but 97 vs 80 us at 140^2 x 2
-        # (324 tiles of 128 pixels on 256 CUs: one and a quarter rounds)
-        wide = Dp == 576 and dtype == torch.float16 and os.environ.get("ROMA_WIDE_BLOCK", "1") != "0"
-        blocks = []
+        # every implementation block_impl can pick for this level: its answer on the smallest map and on one that fills the chip
+        blocks = {impl: [] for impl in (block_impl(Dp, dtype, 1, 1, 1), block_impl(Dp, dtype, 512, 8, 16))}
         for blk in [self.block1] + list(self.hidden_blocks):
             dw, bn, _, pw = blk
             s = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
@@ -109,32 +128,26 @@ class ConvRefiner(nn.Module):
             wt[:D, :D] = pw.weight.float().reshape(D, D).t()            # (in, out): X @ wt
             b = torch.zeros(Dp, device=dev)
             b[:D] = pw.bias.float()
-            if wide:
-                blocks.append((w25.contiguous(), scale, shift, wt.to(dtype).contiguous(), b.to(dtype),
-                               ops.refiner_wide_taps(w25, dtype), ops.refiner_wide_pack(wt.t().contiguous().to(dtype)), b.contiguous()))
-            elif fused:
-                # one kernel per block (ops.refiner_block): weights zero-padded to kpad channels, 1x1 weight as [out][in]
-                kp = 32 if Dp <= 32 else 160
-                blocks.append((_zero_pad(w25, 25, kp).to(dtype), _zero_pad(scale, kp), _zero_pad(shift, kp),
-                               _zero_pad(wt.t(), kp, kp).to(dtype), _zero_pad(b, kp)))
-            elif mid:
-                # mid widths (D = 144): depthwise kernel + streaming MFMA 1x1 (ops.pointwise_mfma), weight [out][in] padded to 160
-                blocks.append((w25.contiguous(), scale, shift, _zero_pad(wt.t(), 160, 160).to(dtype), _zero_pad(b, 160)))
-            # narrow refiners (Dp <= 32): the 1x1 conv is a streaming op -> own kernel with fp32 weights; else a library GEMM
-            elif Dp <= 32:
-                blocks.append((w25.contiguous(), scale, shift, wt.contiguous(), b.contiguous()))
-            else:
-                blocks.append((w25.contiguous(), scale, shift, wt.to(dtype).contiguous(), b.to(dtype)))
+            for impl, out in blocks.items():
+                if impl == "wide":
+                    out.append(BlockWide(ops.refiner_wide_taps(w25, dtype), scale, shift, ops.refiner_wide_pack(wt.t().contiguous().to(dtype)), b))
+                elif impl == "fused":
+                    out.append(BlockOutIn(_zero_pad(w25, 25, 32).to(dtype), _zero_pad(scale, 32), _zero_pad(shift, 32),
+                                          _zero_pad(wt.t(), 32, 32).to(dtype), _zero_pad(b, 32)))
+                elif impl == "split_mfma":
+                    out.append(BlockOutIn(w25, scale, shift, _zero_pad(wt.t(), 160, 160).to(dtype), _zero_pad(b, 160)))
+                else:                                                   # split_small (fp32 only: the weights stay fp32), split_gemm
+                    out.append(BlockInOut(w25, scale, shift, wt.to(dtype), b.to(dtype)))
         wo = torch.zeros(Dp, self.out_dim, device=dev)
         wo[:D] = self.out_conv.weight.float().reshape(self.out_dim, D).t()
-        prep = dict(D=D, Dp=Dp, fused=fused, mid=mid, wide=wide, blocks=blocks, wo=wo.contiguous(), bo=self.out_conv.bias.float(),
-                    we=self.disp_emb.weight.float().reshape(-1, 2).contiguous(), be=self.disp_emb.bias.float())
+        prep = RefinerPlan(D, Dp, blocks, wo.contiguous(), self.out_conv.bias.float(),
+                           self.disp_emb.weight.float().reshape(-1, 2).contiguous(), self.disp_emb.bias.float())
         self._prep = (key, prep)
         return prep
 
     def new_buffer(self, B, h, w, dtype, device):
         """The channels-last (B,h,w,Dp) concat buffer of one forward; the caller may fill channels [0, C) with x itself."""
-        return torch.empty((B, h, w, self.prepare(dtype)["Dp"]), dtype=dtype, device=device)
+        return torch.empty((B, h, w, self.prepare(dtype).Dp), dtype=dtype, device=device)
 
     @torch.no_grad()
     def _body(self, x, y, flow, scale_factor, dtype, buf=None, batch_shift=0):
@@ -142,8 +155,8 @@ class ConvRefiner(nn.Module):
         batch_shift: x[b] is matched against y[(b + batch_shift) % B] (forward_symmetric passes y = x, shift = B/2)."""
         P = self.prepare(dtype)
         B, C, h, w = x.shape
-        D, Dp = P["D"], P["Dp"]
-        E = P["we"].shape[0]
+        D, Dp = P.D, P.Dp
+        E = P.we.shape[0]
         r = self.local_corr_radius
         K = (2 * r + 1) ** 2 if r else 0
         assert 2 * C + E + K == D, "feature width does not match this refiner"
@@ -160,32 +173,29 @@ class ConvRefiner(nn.Module):
             buf[..., D:].zero_()
         yy = y.to(dtype)
         ops.warp_bilinear(yy, flow, out=d[:, C:2 * C], batch_shift=batch_shift)               # matcher.py:109
-        ops.disp_emb(flow, P["we"], P["be"], 40 / 32 * scale_factor, out=d[:, 2 * C:2 * C + E])  # :111-120
+        ops.disp_emb(flow, P.we, P.be, 40 / 32 * scale_factor, out=d[:, 2 * C:2 * C + E])      # :111-120
         if r:
             ops.local_correlation(d[:, :C], yy, r, flow=flow, out=d[:, 2 * C + E:D], batch_shift=batch_shift)   # :121-125
-        M = B * h * w
+        impl = block_impl(Dp, dtype, B, h, w)
         cur = buf
-        if P["wide"] and B * ((h + 7) // 8) * ((w + 15) // 16) >= 2 * 256:
-            nxt = torch.empty_like(buf)
-            for blk in P["blocks"]:                                                            # :139-140
-                ops.refiner_block_wide(cur, blk[5], blk[1], blk[2], blk[6], blk[7], out=nxt)
+        nxt = torch.empty_like(buf) if impl in ("wide", "fused") else None    # the one-kernel blocks ping-pong between two buffers
+        for blk in P.blocks[impl]:                                                             # :139-140
+            if impl == "wide":
+                ops.refiner_block_wide(cur, blk.taps, blk.scale, blk.shift, blk.wt_panels, blk.bias, out=nxt)
                 cur, nxt = nxt, cur
-            return cur, P
-        if P["fused"]:
-            nxt = torch.empty_like(buf)
-            for (w25, scale, shift, wt, b) in P["blocks"]:                                     # :139-140
-                ops.refiner_block(cur, w25, scale, shift, wt, b, Dp, out=nxt)
+            elif impl == "fused":
+                ops.refiner_block(cur, blk.w25, blk.scale, blk.shift, blk.wt_out_in, blk.bias, Dp, out=nxt)
                 cur, nxt = nxt, cur
-            return cur, P
-        for blk in P["blocks"]:                                                                # :139-140
-            w25, scale, shift, wt, b = blk[:5]
-            t = ops.dwconv5x5_bn_relu(cur.permute(0, 3, 1, 2), w25, scale, shift)
-            rows = t.permute(0, 2, 3, 1).reshape(M, Dp)
-            if P["mid"]:
-                cur = ops.pointwise_mfma(rows, wt, b, Dp)
             else:
-                cur = ops.pointwise_small(rows, wt, b) if Dp <= 32 else torch.addmm(b, rows, wt)
-            cur = cur.view(B, h, w, Dp)
+                t = ops.dwconv5x5_bn_relu(cur.permute(0, 3, 1, 2), blk.w25, blk.scale, blk.shift)
+                rows = t.permute(0, 2, 3, 1).reshape(B * h * w, Dp)
+                if impl == "split_mfma":
+                    cur = ops.pointwise_mfma(rows, blk.wt_out_in, blk.bias, Dp)
+                elif impl == "split_small":
+                    cur = ops.pointwise_small(rows, blk.wt_in_out, blk.bias)
+                else:
+                    cur = torch.addmm(blk.bias, rows, blk.wt_in_out)
+                cur = cur.view(B, h, w, Dp)
         return cur, P
 
     @torch.no_grad()
@@ -195,7 +205,7 @@ class ConvRefiner(nn.Module):
         flow = flow.float().contiguous()
         cur, P = self._body(x, y, flow, scale_factor, dtype or self.amp_dtype)
         B, h, w, Dp = cur.shape
-        out = torch.addmm(P["bo"], cur.reshape(B * h * w, Dp).float(), P["wo"])                # out_conv in fp32, :141
+        out = torch.addmm(P.bo, cur.reshape(B * h * w, Dp).float(), P.wo)                    # out_conv in fp32, :141
         out = out.view(B, h, w, self.out_dim).permute(0, 3, 1, 2).contiguous()
         return out[:, :-1], out[:, -1:]
 
@@ -204,7 +214,7 @@ class ConvRefiner(nn.Module):
         """The Decoder's use of the refiner (matcher.py:393-402) with out_conv fused into the update kernel:
         flow (B,2,h,w) fp32 contiguous is updated IN PLACE by (sx*dx, sy*dy); returns (flow, certainty + dcert)."""
         cur, P = self._body(x, y, flow, scale_factor, dtype or self.amp_dtype, buf=buf, batch_shift=batch_shift)
-        return ops.refiner_head(cur, P["wo"], P["bo"], flow, certainty, sx, sy)
+        return ops.refiner_head(cur, P.wo, P.bo, flow, certainty, sx, sy)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -72,13 +72,62 @@ def test_refiner_bn_folding_algebra():
     x = torch.randn(1, 24, 9, 11)
     dw, bn, _, pw = r.block1
     ref = F.relu(bn(dw(x)))
-    w25, scale, shift, wt, b = P["blocks"][0]
-    conv = F.conv2d(x, w25.t().reshape(24, 1, 5, 5), None, 1, 2, groups=24)
-    mine = F.relu(conv * scale[None, :, None, None] + shift[None, :, None, None])
+    blk = P.blocks["split_small"][0]
+    conv = F.conv2d(x, blk.w25.t().reshape(24, 1, 5, 5), None, 1, 2, groups=24)
+    mine = F.relu(conv * blk.scale[None, :, None, None] + blk.shift[None, :, None, None])
     assert float((mine - ref).abs().max()) < 1e-5
     ref2 = pw(ref)
-    mine2 = (mine.permute(0, 2, 3, 1).reshape(-1, 24) @ wt + b).reshape(1, 9, 11, 24).permute(0, 3, 1, 2)
+    mine2 = (mine.permute(0, 2, 3, 1).reshape(-1, 24) @ blk.wt_in_out + blk.bias).reshape(1, 9, 11, 24).permute(0, 3, 1, 2)
     assert float((mine2 - ref2).abs().max()) < 1e-5
+
+
+def test_refiner_block_impl_table():
+    """Which implementation runs the blocks of each shipped refiner at the product shapes (560 -> 864, B = 2), per amp dtype, and
+    the tile-count boundary of the wide kernel.  Only the decision function is called: no tensors, no library."""
+    from roma_amd.matcher import block_impl, padded_width
+    from roma_amd.model_zoo import REFINER_SPEC
+    Dp = {int(s): padded_width(2 * fd + ed + ((2 * r + 1) ** 2 if r else 0)) for s, (fd, ed, r) in REFINER_SPEC.items()}
+    assert Dp == {16: 1408, 8: 1152, 4: 576, 2: 144, 1: 24}
+    coarse = {16: 40, 8: 70, 4: 140, 2: 280, 1: 560}
+    upsample = {8: 108, 4: 216, 2: 432, 1: 864}
+    expected = {
+        torch.float16: {16: "split_gemm", 8: "split_gemm", 4: "split_gemm", 2: "split_mfma", 1: "fused"},
+        torch.bfloat16: {16: "split_gemm", 8: "split_gemm", 4: "split_gemm", 2: "split_mfma", 1: "fused"},
+        torch.float32: {16: "split_gemm", 8: "split_gemm", 4: "split_gemm", 2: "split_gemm", 1: "split_small"},
+    }
+    for dtype, want in expected.items():
+        for sizes in (coarse, upsample):
+            for s, n in sizes.items():
+                wide = dtype == torch.float16 and (s, n) == (4, 216)        # the only product level / shape on the wide kernel
+                assert block_impl(Dp[s], dtype, 2, n, n) == ("wide" if wide else want[s]), (dtype, s, n)
+    assert block_impl(576, torch.float16, 2, 128, 256) == "wide"            # 2 * 16 * 16 = 512 tiles
+    assert block_impl(576, torch.float16, 2, 128, 240) == "split_gemm"      # 480 tiles
+    assert block_impl(576, torch.float16, 1, 216, 216) == "split_gemm"      # 27 * 14 = 378 tiles
+
+
+def test_refiner_prepare_records_and_removed_env_options(monkeypatch):
+    """The D = 576 refiner carries the records of both of its implementations in fp16 and only the split one in bf16, and the four
+    removed environment options select nothing any more."""
+    from roma_amd.matcher import BlockInOut, BlockWide, ConvRefiner
+    r = ConvRefiner(576, 576, 3, hidden_blocks=1, displacement_emb_dim=32, local_corr_radius=2).eval()
+    H.load_recipe_weights(r, "plan.")
+
+    def plans():
+        r._prep = None
+        return r.prepare(torch.float16), r.prepare(torch.bfloat16)
+
+    p16, pbf = plans()
+    assert set(p16.blocks) == {"wide", "split_gemm"} and set(pbf.blocks) == {"split_gemm"}
+    assert len(p16.blocks["wide"]) == len(p16.blocks["split_gemm"]) == len(pbf.blocks["split_gemm"]) == 2
+    assert all(isinstance(b, BlockWide) for b in p16.blocks["wide"])
+    assert all(isinstance(b, BlockInOut) for b in p16.blocks["split_gemm"] + pbf.blocks["split_gemm"])
+    for name, value in (("ROMA_FUSED_BLOCK", "160"), ("ROMA_PW_MFMA", "0"), ("ROMA_WIDE_BLOCK", "0"), ("ROMA_RB_TOEP", "0")):
+        monkeypatch.setenv(name, value)
+        q16, qbf = plans()
+        for p, q in ((p16, q16), (pbf, qbf)):
+            assert p.Dp == q.Dp and set(p.blocks) == set(q.blocks)
+            for impl in p.blocks:
+                assert all(torch.equal(a, b) for ba, bb in zip(p.blocks[impl], q.blocks[impl]) for a, b in zip(ba, bb))
 
 
 def test_proj_folding_algebra():
