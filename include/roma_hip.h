@@ -308,6 +308,19 @@ int roma_ransac_hypotheses(int kind, const double* xa, const double* xb, int P, 
 int roma_ransac_select(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int lo_iters,
                        const void* ws, long ws_bytes, double* model, unsigned char* mask, void* stream);
 
+/* The same with the scoring chosen by the caller: scoring 0 = MSAC (what the two calls above run, bit for bit), 1 = MAGSAC++
+ * ("MAGSAC++ scoring"); any other value returns ROMA_E_ARG.  `threshold` keeps its meaning — the residual above which
+ * a match is an outlier, mask = error < threshold^2 — and is the UPPER BOUND of the noise scale: with u = error / threshold^2 a slot
+ * costs threshold^2 * sum of L(u) (L = 1 beyond the threshold) and the local optimisation is iteratively re-weighted least squares
+ * with weights W(u), L and W the piecewise-linear interpolants of the 1 025 nodes u_j = j / 1024 that roma_magsac_table copies.  Both
+ * calls of one estimate take the same scoring.  Workspace layout, regions and outputs are unchanged (region [7] is the chosen cost).
+ * roma_magsac_table: host function; copies the nodes L(u_j) and W(u_j) into two caller arrays of 1 025 floats. */
+int roma_ransac_hypotheses_ex(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int scoring,
+                              unsigned seed, int p0, void* ws, long ws_bytes, void* stream);
+int roma_ransac_select_ex(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int scoring,
+                          int lo_iters, const void* ws, long ws_bytes, double* model, unsigned char* mask, void* stream);
+int roma_magsac_table(float* loss, float* weight);
+
 /* Calibrated two-view geometry — replaces estimate_pose of the reference (romatch/utils/utils.py:31-52:
  * cv2.findEssentialMat on calibrated points, then cv2.recoverPose), which its MegaDepth-1500 and ScanNet-1500 benchmarks call.
  * xa, xb: (P,N,2) fp64 PIXEL coordinates; Ka, Kb: (P,3,3) fp64 intrinsics, upper triangular with last row 0 0 1.  The estimator
@@ -336,6 +349,14 @@ int roma_essential_select(const double* xa, const double* xb, const double* Ka, 
 int roma_recover_pose(const double* xa, const double* xb, const double* Ka, const double* Kb, const double* E,
                       const unsigned char* mask_in, int P, int N, double* R, double* t, int* count, unsigned char* mask_out,
                       void* stream);
+
+/* roma_essential_hypotheses / roma_essential_select with the scoring chosen by the caller, as roma_ransac_*_ex above (0 = MSAC, 1 =
+ * MAGSAC++; the re-weighted refit is projected onto the essential manifold as the unweighted one is). */
+int roma_essential_hypotheses_ex(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N, int iters,
+                                 float threshold, int scoring, unsigned seed, int p0, void* ws, long ws_bytes, void* stream);
+int roma_essential_select_ex(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N, int iters,
+                             float threshold, int scoring, int lo_iters, const void* ws, long ws_bytes, double* E, unsigned char* mask,
+                             void* stream);
 
 /* Non-linear refinement of a relative pose (csrc/pose_refine.hip) — the Levenberg-Marquardt stage behind the RANSAC
  * of poselib.estimate_relative_pose, which the reference's PoseLib benchmark calls.  Points and intrinsics as roma_recover_pose

@@ -12,6 +12,7 @@ ROMA_F32, ROMA_F16, ROMA_BF16 = 0, 1, 2
 ROMA_NCHW, ROMA_NHWC = 0, 1
 LC_VARIANTS = {"auto": 0, "tile8x4": 1, "tile8x8": 2, "rows8": 3}
 ABI_VERSION = 5
+SCORE_MSAC, SCORE_MAGSAC = 0, 1                            # the `scoring` argument of the roma_*_ex estimator calls
 ROMA_E_ARG, ROMA_E_DTYPE, ROMA_E_SHAPE, ROMA_E_ALIGN, ROMA_E_UNSUPPORTED = -1, -2, -3, -4, -5      # include/roma_hip.h
 
 # name -> argtypes; restype is c_int unless listed in _RESTYPES.  Mirrors include/roma_hip.h one to one.
@@ -65,11 +66,20 @@ SIGNATURES = {
     "roma_ransac_hypotheses": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, ctypes.c_uint, c_int, c_void_p, c_long, c_void_p],
     "roma_ransac_select": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_long, c_void_p, c_void_p,
                            c_void_p],
+    "roma_ransac_hypotheses_ex": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, ctypes.c_uint, c_int, c_void_p, c_long,
+                                  c_void_p],
+    "roma_ransac_select_ex": [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p,
+                              c_void_p],
+    "roma_magsac_table": [c_void_p, c_void_p],
     "roma_essential_workspace": [c_int, c_int, c_int, c_void_p],
     "roma_essential_hypotheses": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, ctypes.c_uint, c_int, c_void_p,
                                   c_long, c_void_p],
     "roma_essential_select": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_long, c_void_p,
                               c_void_p, c_void_p],
+    "roma_essential_hypotheses_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, ctypes.c_uint, c_int,
+                                     c_void_p, c_long, c_void_p],
+    "roma_essential_select_ex": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_long,
+                                 c_void_p, c_void_p, c_void_p],
     "roma_recover_pose": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                           c_void_p, c_void_p],
     "roma_refine_pose": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int,

@@ -1,7 +1,8 @@
 // Calibrated two-view geometry: RANSAC for essential matrices (5-point minimal solver) and relative pose recovery.  Replaces
 // estimate_pose of the reference (romatch/utils/utils.py:31-52: cv2.findEssentialMat on calibrated points, then cv2.recoverPose),
-// which both pose benchmarks call.  Same ground rules as geometry.hip: fp64 minimal solver, fp32 MSAC scoring of every slot, fixed
-// number of samples, no atomics, no host synchronisation, bitwise reproducible.  DESIGN.md §3.4.
+// which both pose benchmarks call.  Same ground rules as geometry.hip: fp64 minimal solver, fp32 scoring of every slot (MSAC, or
+// MAGSAC++ through the *_ex entry points), fixed number of samples, no atomics, no host synchronisation, bitwise reproducible.
+// DESIGN.md §3.4.
 //
 // Pipeline, one call of roma_essential_hypotheses + one of roma_essential_select (P pairs of N matches, H = iters samples each):
 //   calibrate_kernel         one block/pair   x_hat = K^-1 x in fp64 (both images) + the fp32 copy the scoring reads (NaN where a match
@@ -10,7 +11,8 @@
 //   score_kernel<KIND_F>     an E in calibrated coordinates is an F: the scoring of geometry.hip on iters * 10 slots, ka = kb = 1
 //   reduce_kernel            (ransac_common.h)
 //   essential_select_kernel  one block/pair   lowest cost, lo_iters rounds of least squares on the inliers projected onto the
-//                                             essential manifold, kept only if the MSAC cost drops; E with singular values (s, s, 0)
+//                                             essential manifold (weighted by W for MAGSAC++), kept only if the cost drops; E with
+//                                             singular values (s, s, 0)
 // and, on its own, recover_pose_kernel (one block/pair): the four (R, t) of E, cheirality vote over the masked matches.
 //
 // The 5-point solver (Nistér 2004, hidden-variable finish: the degree-10 polynomial in z).  One sample is solved by a group of 32
@@ -581,6 +583,7 @@ __device__ __forceinline__ bool finite9(const double* m) {
   return fin;
 }
 
+template <int SCORE>
 __global__ __launch_bounds__(256) void essential_select_kernel(const double* __restrict__ xh, const float4* __restrict__ pts,
                                                                const double* __restrict__ models, const double* __restrict__ cost,
                                                                int N, int M, float t2, int lo_iters, double* __restrict__ out_model,
@@ -620,7 +623,7 @@ __global__ __launch_bounds__(256) void essential_select_kernel(const double* __r
   __syncthreads();
   double cc;
   int cn;
-  block_score<KIND_F>(cur, pq, N, 1.f, 1.f, t2, dred, ired, cc, cn);
+  block_score<KIND_F, SCORE>(cur, pq, N, 1.f, 1.f, t2, dred, ired, cc, cn);
 
   // 2. local optimisation: least squares on the inliers, projected onto the essential manifold, kept only if its cost is lower
   for (int round = 0; round < lo_iters; ++round) {
@@ -632,10 +635,13 @@ __global__ __launch_bounds__(256) void essential_select_kernel(const double* __r
 #pragma unroll
     for (int i = 0; i < 45; ++i) acc[i] = 0.0;
     for (int i = tid; i < N; i += 256) {
-      if (!(point_error<KIND_F>(m, pq[i], 1.f, 1.f) < t2)) continue;
+      const float e = point_error<KIND_F>(m, pq[i], 1.f, 1.f);
+      if (!(e < t2)) continue;
       const double* q = xh + ((size_t)p * N + i) * 4;
       const double x = q[0], y = q[1], u = q[2], v = q[3];
-      const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+      double sw = 1.0;                                              // SCORE_MAGSAC: rows scaled by sqrt W under the current model
+      if constexpr (SCORE == SCORE_MAGSAC) sw = sqrt((double)magsac_lookup(magsac_weight_cells, e, (float)MAGSAC_CELLS / t2));
+      const double a[9] = {sw * (u * x), sw * (u * y), sw * u, sw * (v * x), sw * (v * y), sw * v, sw * x, sw * y, sw};
       int k = 0;
 #pragma unroll
       for (int r = 0; r < 9; ++r)
@@ -670,7 +676,7 @@ __global__ __launch_bounds__(256) void essential_select_kernel(const double* __r
     if (!finite9(cand)) break;                                    // block-uniform (LDS)
     double c2;
     int n2;
-    block_score<KIND_F>(cand, pq, N, 1.f, 1.f, t2, dred, ired, c2, n2);
+    block_score<KIND_F, SCORE>(cand, pq, N, 1.f, 1.f, t2, dred, ired, c2, n2);
     if (!(c2 < cc)) break;
     if (tid < 9) cur[tid] = cand[tid];
     __syncthreads();
@@ -864,11 +870,15 @@ extern "C" long roma_essential_workspace(int P, int N, int iters, long* offsets)
   return layout_e(P, N, iters, offsets);
 }
 
-extern "C" int roma_essential_hypotheses(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N,
-                                         int iters, float threshold, unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
-  const int rc = check_args_e(__func__, xa, xb, Ka, Kb, ws, P, N, iters, threshold, ws_bytes);
+namespace {
+
+int essential_hypotheses(const char* fn, const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N, int iters,
+                         float threshold, int scoring, unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
+  int rc = check_args_e(fn, xa, xb, Ka, Kb, ws, P, N, iters, threshold, ws_bytes);
   if (rc) return rc;
-  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "roma_essential_hypotheses: negative pair offset %d", p0);
+  rc = check_scoring(fn, scoring);
+  if (rc) return rc;
+  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "%s: negative pair offset %d", fn, p0);
   long off[WE_N];
   layout_e(P, N, iters, off);
   char* w = static_cast<char*>(ws);
@@ -892,27 +902,58 @@ extern "C" int roma_essential_hypotheses(const double* xa, const double* xb, con
   hipLaunchKernelGGL(calibrate_kernel, dim3(P), dim3(256), 0, st, xa, xb, Ka, Kb, N, norm, pts, xh);
   hipLaunchKernelGGL(five_point_kernel, gm, dim3(256), 0, st, (const double*)xh, (const float*)pts, P, N, iters, sstream, p0, samples,
                      models, valid);
-  hipLaunchKernelGGL(score_kernel<KIND_F>, gs, dim3(256), 0, st, (const float4*)pts, (const double*)norm, (const double*)models,
-                     (const int*)valid, N, M, t2, slab_cost, slab_cnt);
+  auto score = score_kernel<KIND_F, SCORE_MSAC>;
+  if (scoring == SCORE_MAGSAC) score = score_kernel<KIND_F, SCORE_MAGSAC>;
+  hipLaunchKernelGGL(score, gs, dim3(256), 0, st, (const float4*)pts, (const double*)norm, (const double*)models, (const int*)valid, N, M,
+                     t2, slab_cost, slab_cnt);
   hipLaunchKernelGGL(reduce_kernel, gr, dim3(256), 0, st, (const float*)slab_cost, (const int*)slab_cnt, (const int*)valid, P, M, C,
                      cost, count);
-  ROMA_CHECK_LAUNCH();
+  return check_launch(fn);
+}
+
+int essential_select(const char* fn, const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N, int iters,
+                     float threshold, int scoring, int lo_iters, const void* ws, long ws_bytes, double* E, unsigned char* mask,
+                     void* stream) {
+  int rc = check_args_e(fn, xa, xb, Ka, Kb, ws, P, N, iters, threshold, ws_bytes);
+  if (rc) return rc;
+  ROMA_REQUIRE(E && mask, ROMA_E_ARG, "%s: null pointer", fn);
+  rc = check_scoring(fn, scoring);
+  if (rc) return rc;
+  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "%s: negative lo_iters %d", fn, lo_iters);
+  long off[WE_N];
+  layout_e(P, N, iters, off);
+  const char* w = static_cast<const char*>(ws);
+  auto sel = essential_select_kernel<SCORE_MSAC>;
+  if (scoring == SCORE_MAGSAC) sel = essential_select_kernel<SCORE_MAGSAC>;
+  hipLaunchKernelGGL(sel, dim3(P), dim3(256), 0, static_cast<hipStream_t>(stream), (const double*)(w + off[WE_XH]),
+                     (const float4*)(w + off[WE_PTS]), (const double*)(w + off[WE_MODELS]), (const double*)(w + off[WE_COST]), N,
+                     iters * E_R, threshold * threshold, lo_iters, E, mask);
+  return check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" int roma_essential_hypotheses(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N,
+                                         int iters, float threshold, unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
+  return essential_hypotheses(__func__, xa, xb, Ka, Kb, P, N, iters, threshold, SCORE_MSAC, seed, p0, ws, ws_bytes, stream);
+}
+
+extern "C" int roma_essential_hypotheses_ex(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N,
+                                            int iters, float threshold, int scoring, unsigned seed, int p0, void* ws, long ws_bytes,
+                                            void* stream) {
+  return essential_hypotheses(__func__, xa, xb, Ka, Kb, P, N, iters, threshold, scoring, seed, p0, ws, ws_bytes, stream);
 }
 
 extern "C" int roma_essential_select(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N, int iters,
                                      float threshold, int lo_iters, const void* ws, long ws_bytes, double* E, unsigned char* mask,
                                      void* stream) {
-  const int rc = check_args_e(__func__, xa, xb, Ka, Kb, ws, P, N, iters, threshold, ws_bytes);
-  if (rc) return rc;
-  ROMA_REQUIRE(E && mask, ROMA_E_ARG, "roma_essential_select: null pointer");
-  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "roma_essential_select: negative lo_iters %d", lo_iters);
-  long off[WE_N];
-  layout_e(P, N, iters, off);
-  const char* w = static_cast<const char*>(ws);
-  hipLaunchKernelGGL(essential_select_kernel, dim3(P), dim3(256), 0, static_cast<hipStream_t>(stream), (const double*)(w + off[WE_XH]),
-                     (const float4*)(w + off[WE_PTS]), (const double*)(w + off[WE_MODELS]), (const double*)(w + off[WE_COST]), N,
-                     iters * E_R, threshold * threshold, lo_iters, E, mask);
-  ROMA_CHECK_LAUNCH();
+  return essential_select(__func__, xa, xb, Ka, Kb, P, N, iters, threshold, SCORE_MSAC, lo_iters, ws, ws_bytes, E, mask, stream);
+}
+
+extern "C" int roma_essential_select_ex(const double* xa, const double* xb, const double* Ka, const double* Kb, int P, int N, int iters,
+                                        float threshold, int scoring, int lo_iters, const void* ws, long ws_bytes, double* E,
+                                        unsigned char* mask, void* stream) {
+  return essential_select(__func__, xa, xb, Ka, Kb, P, N, iters, threshold, scoring, lo_iters, ws, ws_bytes, E, mask, stream);
 }
 
 extern "C" int roma_recover_pose(const double* xa, const double* xb, const double* Ka, const double* Kb, const double* E,

@@ -1,4 +1,5 @@
-// Robust two-view geometry: RANSAC (MSAC scoring + least-squares local optimisation) for fundamental matrices (7-point) and
+// Robust two-view geometry: RANSAC (MSAC scoring + least-squares local optimisation; on request MAGSAC++ scoring + iteratively
+// re-weighted least squares, the *_ex entry points) for fundamental matrices (7-point) and
 // homographies (4-point DLT).  Replaces the estimator every caller of the reference runs after match -> sample ->
 // to_pixel_coordinates: cv2.findFundamentalMat (demo/demo_fundamental.py:28-34, romatch/utils/utils.py:54-62) and
 // cv2.findHomography (romatch/benchmarks/hpatches_sequences_homog_benchmark.py:72-86).  DESIGN.md §3.4.
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(128) void minimal_kernel(const double* __restrict__
   }
 }
 
-template <int KIND>
+template <int KIND, int SCORE>
 __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ xa, const double* __restrict__ xb,
                                                      const float4* __restrict__ pts, const double* __restrict__ norm,
                                                      const double* __restrict__ models, const double* __restrict__ cost, int N, int M,
@@ -327,9 +328,10 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
   error_scales<KIND>(nrm, ka, kb);
   double cc;
   int cn;
-  block_score<KIND>(cur, pq, N, ka, kb, t2, dred, ired, cc, cn);
+  block_score<KIND, SCORE>(cur, pq, N, ka, kb, t2, dred, ired, cc, cn);
 
-  // 2. local optimisation: least-squares refit on the inliers, kept only if its cost is lower
+  // 2. local optimisation: least-squares refit on the inliers (SCORE_MAGSAC: weighted by W under the current model, the rows scaled
+  // by sqrt W), kept only if its cost is lower
   const double cxA = nrm[0], cyA = nrm[1], sA = nrm[2], cxB = nrm[4], cyB = nrm[5], sB = nrm[6];
   for (int round = 0; round < lo_iters; ++round) {
     if (cn < Kind<KIND>::LO_MIN) break;
@@ -340,19 +342,30 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 45; ++i) acc[i] = 0.0;
     for (int i = tid; i < N; i += 256) {
-      if (!(point_error<KIND>(m, pq[i], ka, kb) < t2)) continue;
+      const float e = point_error<KIND>(m, pq[i], ka, kb);
+      if (!(e < t2)) continue;
       const size_t q = ((size_t)p * N + i) * 2;
       const double x = (xa[q] - cxA) * sA, y = (xa[q + 1] - cyA) * sA, u = (xb[q] - cxB) * sB, v = (xb[q + 1] - cyB) * sB;
+      double sw = 1.0;
+      if constexpr (SCORE == SCORE_MAGSAC) sw = sqrt((double)magsac_lookup(magsac_weight_cells, e, (float)MAGSAC_CELLS / t2));
       if constexpr (KIND == KIND_F) {
-        const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+        double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+        if constexpr (SCORE == SCORE_MAGSAC) {
+#pragma unroll
+          for (int r = 0; r < 9; ++r) a[r] *= sw;
+        }
         int k = 0;
 #pragma unroll
         for (int r = 0; r < 9; ++r)
 #pragma unroll
           for (int c = r; c < 9; ++c) { acc[k] = __builtin_fma(a[r], a[c], acc[k]); ++k; }
       } else {
-        const double a[9] = {x, y, 1.0, 0.0, 0.0, 0.0, -u * x, -u * y, -u};
-        const double b[9] = {0.0, 0.0, 0.0, x, y, 1.0, -v * x, -v * y, -v};
+        double a[9] = {x, y, 1.0, 0.0, 0.0, 0.0, -u * x, -u * y, -u};
+        double b[9] = {0.0, 0.0, 0.0, x, y, 1.0, -v * x, -v * y, -v};
+        if constexpr (SCORE == SCORE_MAGSAC) {
+#pragma unroll
+          for (int r = 0; r < 9; ++r) { a[r] *= sw; b[r] *= sw; }
+        }
         int k = 0;
 #pragma unroll
         for (int r = 0; r < 9; ++r)
@@ -415,7 +428,7 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
     if (!fin) break;                                              // block-uniform (LDS)
     double c2;
     int n2;
-    block_score<KIND>(cand, pq, N, ka, kb, t2, dred, ired, c2, n2);
+    block_score<KIND, SCORE>(cand, pq, N, ka, kb, t2, dred, ired, c2, n2);
     if (!(c2 < cc)) break;
     if (tid < 9) cur[tid] = cand[tid];
     __syncthreads();
@@ -529,13 +542,16 @@ extern "C" long roma_ransac_workspace(int kind, int P, int N, int iters, long* o
   return layout(kind, P, N, iters, offsets);
 }
 
-extern "C" int roma_ransac_hypotheses(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold,
-                                      unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
-  const int rc = check_args(__func__, kind, xa, xb, ws, P, N, iters, ws_bytes);
+namespace {
+
+int ransac_hypotheses(const char* fn, int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold,
+                      int scoring, unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
+  int rc = check_args(fn, kind, xa, xb, ws, P, N, iters, ws_bytes);
   if (rc) return rc;
-  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "roma_ransac_hypotheses: threshold must be positive, got %g",
-               (double)threshold);
-  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "roma_ransac_hypotheses: negative pair offset %d", p0);
+  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
+  rc = check_scoring(fn, scoring);
+  if (rc) return rc;
+  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "%s: negative pair offset %d", fn, p0);
   long off[WS_N];
   layout(kind, P, N, iters, off);
   char* w = static_cast<char*>(ws);
@@ -557,25 +573,28 @@ extern "C" int roma_ransac_hypotheses(int kind, const double* xa, const double* 
   const long nt = (long)P * iters;
   const dim3 gm((unsigned)((nt + 127) / 128)), gs((unsigned)((M + 255) / 256), (unsigned)C, (unsigned)P);
   const dim3 gr((unsigned)(((long)P * M + 255) / 256));
-  if (kind == KIND_F) {
+  if (kind == KIND_F)
     hipLaunchKernelGGL(minimal_kernel<KIND_F>, gm, dim3(128), 0, st, xa, xb, norm, pts, P, N, iters, sstream, p0, samples, models, valid);
-    hipLaunchKernelGGL(score_kernel<KIND_F>, gs, dim3(256), 0, st, (const float4*)pts, norm, models, valid, N, M, t2, slab_cost, slab_cnt);
-  } else {
+  else
     hipLaunchKernelGGL(minimal_kernel<KIND_H>, gm, dim3(128), 0, st, xa, xb, norm, pts, P, N, iters, sstream, p0, samples, models, valid);
-    hipLaunchKernelGGL(score_kernel<KIND_H>, gs, dim3(256), 0, st, (const float4*)pts, norm, models, valid, N, M, t2, slab_cost, slab_cnt);
-  }
+  auto score = score_kernel<KIND_F, SCORE_MSAC>;
+  if (kind == KIND_F && scoring == SCORE_MAGSAC) score = score_kernel<KIND_F, SCORE_MAGSAC>;
+  if (kind == KIND_H) score = scoring == SCORE_MAGSAC ? score_kernel<KIND_H, SCORE_MAGSAC> : score_kernel<KIND_H, SCORE_MSAC>;
+  hipLaunchKernelGGL(score, gs, dim3(256), 0, st, (const float4*)pts, (const double*)norm, (const double*)models, (const int*)valid, N, M,
+                     t2, slab_cost, slab_cnt);
   hipLaunchKernelGGL(reduce_kernel, gr, dim3(256), 0, st, slab_cost, slab_cnt, valid, P, M, C, cost, count);
-  ROMA_CHECK_LAUNCH();
+  return check_launch(fn);
 }
 
-extern "C" int roma_ransac_select(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int lo_iters,
-                                  const void* ws, long ws_bytes, double* model, unsigned char* mask, void* stream) {
-  const int rc = check_args(__func__, kind, xa, xb, ws, P, N, iters, ws_bytes);
+int ransac_select(const char* fn, int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int scoring,
+                  int lo_iters, const void* ws, long ws_bytes, double* model, unsigned char* mask, void* stream) {
+  int rc = check_args(fn, kind, xa, xb, ws, P, N, iters, ws_bytes);
   if (rc) return rc;
-  ROMA_REQUIRE(model && mask, ROMA_E_ARG, "roma_ransac_select: null pointer");
-  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "roma_ransac_select: threshold must be positive, got %g",
-               (double)threshold);
-  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "roma_ransac_select: negative lo_iters %d", lo_iters);
+  ROMA_REQUIRE(model && mask, ROMA_E_ARG, "%s: null pointer", fn);
+  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
+  rc = check_scoring(fn, scoring);
+  if (rc) return rc;
+  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "%s: negative lo_iters %d", fn, lo_iters);
   long off[WS_N];
   layout(kind, P, N, iters, off);
   const char* w = static_cast<const char*>(ws);
@@ -586,9 +605,37 @@ extern "C" int roma_ransac_select(int kind, const double* xa, const double* xb, 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int M = iters * (kind == KIND_F ? 3 : 1);
   const float t2 = threshold * threshold;
-  if (kind == KIND_F)
-    hipLaunchKernelGGL(select_kernel<KIND_F>, dim3(P), dim3(256), 0, st, xa, xb, pts, norm, models, cost, N, M, t2, lo_iters, model, mask);
-  else
-    hipLaunchKernelGGL(select_kernel<KIND_H>, dim3(P), dim3(256), 0, st, xa, xb, pts, norm, models, cost, N, M, t2, lo_iters, model, mask);
-  ROMA_CHECK_LAUNCH();
+  auto sel = select_kernel<KIND_F, SCORE_MSAC>;
+  if (kind == KIND_F && scoring == SCORE_MAGSAC) sel = select_kernel<KIND_F, SCORE_MAGSAC>;
+  if (kind == KIND_H) sel = scoring == SCORE_MAGSAC ? select_kernel<KIND_H, SCORE_MAGSAC> : select_kernel<KIND_H, SCORE_MSAC>;
+  hipLaunchKernelGGL(sel, dim3(P), dim3(256), 0, st, xa, xb, pts, norm, models, cost, N, M, t2, lo_iters, model, mask);
+  return check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" int roma_ransac_hypotheses(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold,
+                                      unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
+  return ransac_hypotheses(__func__, kind, xa, xb, P, N, iters, threshold, SCORE_MSAC, seed, p0, ws, ws_bytes, stream);
+}
+
+extern "C" int roma_ransac_hypotheses_ex(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold,
+                                         int scoring, unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
+  return ransac_hypotheses(__func__, kind, xa, xb, P, N, iters, threshold, scoring, seed, p0, ws, ws_bytes, stream);
+}
+
+extern "C" int roma_ransac_select(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int lo_iters,
+                                  const void* ws, long ws_bytes, double* model, unsigned char* mask, void* stream) {
+  return ransac_select(__func__, kind, xa, xb, P, N, iters, threshold, SCORE_MSAC, lo_iters, ws, ws_bytes, model, mask, stream);
+}
+
+extern "C" int roma_ransac_select_ex(int kind, const double* xa, const double* xb, int P, int N, int iters, float threshold, int scoring,
+                                     int lo_iters, const void* ws, long ws_bytes, double* model, unsigned char* mask, void* stream) {
+  return ransac_select(__func__, kind, xa, xb, P, N, iters, threshold, scoring, lo_iters, ws, ws_bytes, model, mask, stream);
+}
+
+extern "C" int roma_magsac_table(float* loss, float* weight) {
+  ROMA_REQUIRE(loss && weight, ROMA_E_ARG, "roma_magsac_table: null pointer");
+  for (int i = 0; i < MAGSAC_NODES; ++i) { loss[i] = MAGSAC_LOSS[i]; weight[i] = MAGSAC_WEIGHT[i]; }
+  return 0;
 }

@@ -1,10 +1,12 @@
 // What the RANSAC translation units share (geometry.hip: F / H, essential.hip: E): the counter-hash of the sample draw, the
-// fully unrolled fp64 elimination, fp32 MSAC scoring of every slot (score_kernel / reduce_kernel, no atomics), the block-wide
-// re-score and the LDS Jacobi of the select kernels.  geometry.hip's header pins the draw and the tolerances.  DESIGN.md §3.4.
+// fully unrolled fp64 elimination, fp32 scoring of every slot (score_kernel / reduce_kernel, no atomics; MSAC, or MAGSAC++ by the
+// loss and weight tables of magsac_table.h), the block-wide re-score and the LDS Jacobi of the select kernels.  geometry.hip's
+// header pins the draw and the tolerances.  DESIGN.md §3.4.
 // Plus what the refinement kernels share (pose_refine.hip, fundamental_refine.hip): the Sampson residual written out in fused
 // multiply-adds and the series of exp([w]x).
 #pragma once
 #include "common.h"
+#include "magsac_table.h"
 
 namespace roma {
 namespace {
@@ -181,16 +183,62 @@ template <int KIND> __device__ __forceinline__ void error_scales(const double* n
   kb = KIND == KIND_F ? (float)(sB * sB) : (float)(1.0 / (sB * sB));
 }
 
-// slab_cost / slab_cnt: (P, S, M) with M = iters * R slots and S = ceil(N / CHUNK) chunks
-template <int KIND>
+// MAGSAC++ scoring: loss L and IRLS weight W of u = e / threshold^2 are the piecewise-linear interpolants of the
+// nodes of magsac_table.h.  A cell is {node, next node - node} (one fp32 subtraction); static device data, nothing is copied in a call.
+constexpr int SCORE_MSAC = 0, SCORE_MAGSAC = 1;
+struct MagsacCell { float v, s; };
+struct MagsacCells { MagsacCell c[MAGSAC_CELLS]; };
+constexpr MagsacCells magsac_cells(const float (&t)[MAGSAC_NODES]) {
+  MagsacCells r{};
+  for (int i = 0; i < MAGSAC_CELLS; ++i) { r.c[i].v = t[i]; r.c[i].s = t[i + 1] - t[i]; }
+  return r;
+}
+__device__ const MagsacCells magsac_loss_cells = magsac_cells(MAGSAC_LOSS);
+__device__ const MagsacCells magsac_weight_cells = magsac_cells(MAGSAC_WEIGHT);
+
+// f = e * (1024 / threshold^2) -> cell i = min((int)f, 1023), fraction f - i; the caller has checked e < threshold^2
+__device__ __forceinline__ int magsac_cell(float e, float scale, float& frac) {
+  const float f = e * scale;
+  const int i = min((int)f, MAGSAC_CELLS - 1);
+  frac = f - (float)i;
+  return i;
+}
+__device__ __forceinline__ float magsac_lookup(const MagsacCells& tab, float e, float scale) {
+  float frac;
+  const MagsacCell c = tab.c[magsac_cell(e, scale, frac)];
+  return __builtin_fmaf(frac, c.s, c.v);
+}
+
+// host: what the entry points and their *_ex forms share (fn names the entry point in the message)
+inline int check_scoring(const char* fn, int scoring) {
+  ROMA_REQUIRE(scoring == SCORE_MSAC || scoring == SCORE_MAGSAC, ROMA_E_ARG, "%s: scoring must be 0 (MSAC) or 1 (MAGSAC), got %d", fn,
+               scoring);
+  return 0;
+}
+inline int check_launch(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("%s: %s", fn, hipGetErrorString(e));
+    return (int)e;
+  }
+  return 0;
+}
+
+// slab_cost / slab_cnt: (P, S, M) with M = iters * R slots and S = ceil(N / CHUNK) chunks.  SCORE_MAGSAC: the partial cost is
+// threshold^2 * (outliers of the chunk + sum of L over its inliers).  The loss nodes 0..1023 sit in LDS beside the points (4 KB: with
+// 8 KB of cells a fifth of the workgroups would no longer fit a CU); node 1024 is L(1) = 1.
+template <int KIND, int SCORE>
 __global__ __launch_bounds__(256) void score_kernel(const float4* __restrict__ pts, const double* __restrict__ norm,
                                                     const double* __restrict__ models, const int* __restrict__ valid, int N, int M,
                                                     float t2, float* __restrict__ slab_cost, int* __restrict__ slab_cnt) {
   __shared__ float4 sp[CHUNK];
+  __shared__ float sl[SCORE == SCORE_MAGSAC ? MAGSAC_CELLS : 1];
   const int p = blockIdx.z, s = blockIdx.y, S = gridDim.y;
   const int i0 = s * CHUNK, n = min(CHUNK, N - i0);
   const float4* src = pts + (size_t)p * N + i0;
   for (int i = threadIdx.x; i < n; i += 256) sp[i] = src[i];
+  if constexpr (SCORE == SCORE_MAGSAC)
+    for (int i = threadIdx.x; i < MAGSAC_CELLS; i += 256) sl[i] = magsac_loss_cells.c[i].v;
   __syncthreads();
   const int m = blockIdx.x * 256 + threadIdx.x;
   if (m >= M) return;
@@ -203,11 +251,26 @@ __global__ __launch_bounds__(256) void score_kernel(const float4* __restrict__ p
     for (int i = 0; i < 9; ++i) md[i] = (float)models[slot * 9 + i];
     float ka, kb;
     error_scales<KIND>(norm + p * 8, ka, kb);
-    for (int j = 0; j < n; ++j) {
-      const float e = point_error<KIND>(md, sp[j], ka, kb);
-      const bool in = e < t2;
-      cnt += in ? 1 : 0;
-      cost += in ? e : t2;
+    if constexpr (SCORE == SCORE_MSAC) {
+      for (int j = 0; j < n; ++j) {
+        const float e = point_error<KIND>(md, sp[j], ka, kb);
+        const bool in = e < t2;
+        cnt += in ? 1 : 0;
+        cost += in ? e : t2;
+      }
+    } else {
+      const float scale = (float)MAGSAC_CELLS / t2;
+      for (int j = 0; j < n; ++j) {
+        const float e = point_error<KIND>(md, sp[j], ka, kb);
+        if (e < t2) {                                               // most slot x point pairs are outliers: no lookup
+          float frac;
+          const int i = magsac_cell(e, scale, frac);
+          const float lo = sl[i], hi = sl[min(i + 1, MAGSAC_CELLS - 1)];
+          cost += __builtin_fmaf(frac, (i < MAGSAC_CELLS - 1 ? hi : 1.f) - lo, lo);
+          ++cnt;
+        }
+      }
+      cost = t2 * ((float)(n - cnt) + cost);
     }
   }
   const size_t o = ((size_t)p * S + s) * M + m;
@@ -235,7 +298,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ s
 
 // ---------------------------------------------------------------------------------------------- selection + local optimisation
 // Cost (fp32 errors, fp64 sum in a fixed tree) and inlier count of the model in LDS `mdl` over the pair's N points.
-template <int KIND>
+template <int KIND, int SCORE>
 __device__ void block_score(const double* mdl, const float4* pq, int N, float ka, float kb, float t2, double* dred, int* ired,
                             double& cost, int& cnt) {
   const int tid = threadIdx.x;
@@ -248,8 +311,10 @@ __device__ void block_score(const double* mdl, const float4* pq, int N, float ka
     const float e = point_error<KIND>(m, pq[i], ka, kb);
     const bool in = e < t2;
     n += in ? 1 : 0;
-    c += (double)(in ? e : t2);
+    if constexpr (SCORE == SCORE_MSAC) c += (double)(in ? e : t2);
+    else c += (double)(in ? magsac_lookup(magsac_loss_cells, e, (float)MAGSAC_CELLS / t2) : 1.f);
   }
+  if constexpr (SCORE == SCORE_MAGSAC) c *= (double)t2;
   dred[tid] = c;
   ired[tid] = n;
   __syncthreads();

@@ -7,6 +7,13 @@ lowest cost wins, then least-squares local optimisation (kernel
 drawn and scored; there is no early stop.  The draw is a pure function of the seed (tests/geometry_ref.py restates it).
 No host synchronisation: a call can be captured in a hipGraph.  Tensors must live on a ROCm device; there is no CPU path.
 
+Every estimator takes scoring="msac" (the default, described above) or scoring="magsac": MAGSAC++ sigma-consensus scoring
+(Barath et al., CVPR 2020) and iteratively re-weighted local optimisation.  With "magsac" the threshold is only an UPPER BOUND on the
+noise — the residual above which a match is an outlier, still what the returned mask uses — and the score marginalises over the
+noise scale below it: use it when the noise level is not known and the threshold has to be generous (several times the noise).
+At a threshold already tuned to the noise (about 3 sigma) "msac" is the more accurate one.  DESIGN.md §3.4 has the definition and
+the measurements; parity with OpenCV's USAC_MAGSAC is not claimed (its threshold means something else).
+
 `find_essential`, `recover_pose`, `estimate_pose` and `estimate_pose_uncalibrated` are the calibrated counterpart (csrc/essential.hip):
 the 5-point solver on K^-1 x, the same scoring and selection, local optimisation on the essential manifold, and the cheirality
 vote of cv2.recoverPose — what the reference's pose benchmarks run per pair on the host (romatch/utils/utils.py:12-76).
@@ -73,6 +80,15 @@ def _seed(seed):
     return int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed) & 0xFFFFFFFF
 
 
+def _scoring(scoring):
+    """"msac" / "magsac" -> the C ABI's code; checked before anything looks at a tensor"""
+    if scoring == "msac":
+        return _lib.SCORE_MSAC
+    if scoring == "magsac":
+        return _lib.SCORE_MAGSAC
+    raise ValueError(f"unknown scoring {scoring!r}: 'msac' or 'magsac'")
+
+
 def _args(threshold, max_iters, lo_iters):
     if not threshold > 0:
         raise ValueError(f"threshold must be positive, got {threshold}")
@@ -131,18 +147,19 @@ def _inverse_intrinsics(K):
     return T
 
 
-def _hypotheses(xa, xb, kind, threshold, iters, seed, p0, ws, K=None):
+def _hypotheses(xa, xb, kind, threshold, iters, seed, p0, ws, K=None, score=_lib.SCORE_MSAC):
     P, N = xa.shape[0], xa.shape[1]
     if kind == KIND_E:
-        check(_lib.load().roma_essential_hypotheses(xa.data_ptr(), xb.data_ptr(), K[0].data_ptr(), K[1].data_ptr(), P, N, iters,
-                                                    float(threshold), seed, p0, ws.data_ptr(), ws.numel(), _stream()),
-              "roma_essential_hypotheses")
+        check(_lib.load().roma_essential_hypotheses_ex(xa.data_ptr(), xb.data_ptr(), K[0].data_ptr(), K[1].data_ptr(), P, N, iters,
+                                                       float(threshold), score, seed, p0, ws.data_ptr(), ws.numel(), _stream()),
+              "roma_essential_hypotheses_ex")
         return
-    check(_lib.load().roma_ransac_hypotheses(kind, xa.data_ptr(), xb.data_ptr(), P, N, iters, float(threshold), seed, p0,
-                                             ws.data_ptr(), ws.numel(), _stream()), "roma_ransac_hypotheses")
+    check(_lib.load().roma_ransac_hypotheses_ex(kind, xa.data_ptr(), xb.data_ptr(), P, N, iters, float(threshold), score, seed, p0,
+                                                ws.data_ptr(), ws.numel(), _stream()), "roma_ransac_hypotheses_ex")
 
 
-def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_B=None):
+def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_B=None, scoring="msac"):
+    score = _scoring(scoring)
     _args(threshold, max_iters, lo_iters)
     xa, xb, single = _points(x_A, x_B, kind)
     P, N = xa.shape[0], xa.shape[1]
@@ -159,15 +176,15 @@ def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_
     for a, b in chunks:
         ca, cb = xa[a:b], xb[a:b]
         if kind == KIND_E:
-            _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws, (Ka[a:b], Kb[a:b]))
-            check(lib.roma_essential_select(ca.data_ptr(), cb.data_ptr(), Ka[a:b].data_ptr(), Kb[a:b].data_ptr(), b - a, N, iters,
-                                            float(threshold), int(lo_iters), ws.data_ptr(), total, model[a:b].data_ptr(),
-                                            mask[a:b].data_ptr(), _stream()), "roma_essential_select")
+            _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws, (Ka[a:b], Kb[a:b]), score)
+            check(lib.roma_essential_select_ex(ca.data_ptr(), cb.data_ptr(), Ka[a:b].data_ptr(), Kb[a:b].data_ptr(), b - a, N, iters,
+                                               float(threshold), score, int(lo_iters), ws.data_ptr(), total, model[a:b].data_ptr(),
+                                               mask[a:b].data_ptr(), _stream()), "roma_essential_select_ex")
             continue
-        _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws)
-        check(lib.roma_ransac_select(kind, ca.data_ptr(), cb.data_ptr(), b - a, N, iters, float(threshold), int(lo_iters),
-                                     ws.data_ptr(), total, model[a:b].data_ptr(), mask[a:b].data_ptr(), _stream()),
-              "roma_ransac_select")
+        _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws, None, score)
+        check(lib.roma_ransac_select_ex(kind, ca.data_ptr(), cb.data_ptr(), b - a, N, iters, float(threshold), score, int(lo_iters),
+                                        ws.data_ptr(), total, model[a:b].data_ptr(), mask[a:b].data_ptr(), _stream()),
+              "roma_ransac_select_ex")
     mask = mask.bool()
     return (model[0], mask[0]) if single else (model, mask)
 
@@ -178,26 +195,28 @@ def _refine_iters(refine_iters):
     return int(refine_iters)
 
 
-def find_fundamental(x_A, x_B, threshold=3.0, max_iters=10000, seed=None, lo_iters=3, refine_iters=0):
+def find_fundamental(x_A, x_B, threshold=3.0, max_iters=10000, seed=None, lo_iters=3, refine_iters=0, *, scoring="msac"):
     """Fundamental matrix F (x_B^T F x_A = 0) of pixel correspondences x_A <-> x_B, (N,2) or (P,N,2), fp32/fp64 on the device.
     Returns (F fp64 (3,3) or (P,3,3), unit Frobenius norm, largest-magnitude entry positive; inlier mask bool (N,) or (P,N)):
     Sampson error below threshold (pixels).  All zeros and an empty mask when no sample gives a model.
     refine_iters > 0 polishes the RANSAC model by refine_fundamental on all matches at the same threshold (at most that many
-    Levenberg-Marquardt steps) and returns the refined model's mask; 0, the default, returns the RANSAC model as it is."""
+    Levenberg-Marquardt steps) and returns the refined model's mask; 0, the default, returns the RANSAC model as it is.
+    scoring: "msac" or "magsac" (module docstring); the refinement keeps its truncated Sampson cost either way."""
+    _scoring(scoring)
     refine_iters = _refine_iters(refine_iters)
-    F, mask = _estimate(x_A, x_B, KIND_F, threshold, max_iters, seed, lo_iters)
+    F, mask = _estimate(x_A, x_B, KIND_F, threshold, max_iters, seed, lo_iters, scoring=scoring)
     if refine_iters == 0:
         return F, mask
     return refine_fundamental(F, x_A, x_B, threshold, refine_iters)
 
 
-def find_homography(x_A, x_B, threshold=3.0, max_iters=2000, seed=None, lo_iters=3):
+def find_homography(x_A, x_B, threshold=3.0, max_iters=2000, seed=None, lo_iters=3, *, scoring="msac"):
     """Homography H (x_B ~ H x_A) of pixel correspondences, shapes as find_fundamental.  Returns (H fp64 with H[2,2] = 1 — unit
-    Frobenius norm if |H[2,2]| < 1e-12 |H| —, inlier mask: forward transfer error below threshold)."""
-    return _estimate(x_A, x_B, KIND_H, threshold, max_iters, seed, lo_iters)
+    Frobenius norm if |H[2,2]| < 1e-12 |H| —, inlier mask: forward transfer error below threshold).  scoring: "msac" or "magsac"."""
+    return _estimate(x_A, x_B, KIND_H, threshold, max_iters, seed, lo_iters, scoring=scoring)
 
 
-def find_essential(x_A, x_B, K_A, K_B, threshold, max_iters=2000, seed=None, lo_iters=3):
+def find_essential(x_A, x_B, K_A, K_B, threshold, max_iters=2000, seed=None, lo_iters=3, *, scoring="msac"):
     """Essential matrix E (x_hat_B^T E x_hat_A = 0, x_hat = K^-1 x) of PIXEL correspondences x_A <-> x_B, (N,2) or (P,N,2), fp32/fp64 on
     the device; K_A, K_B: (3,3) (shared by the batch) or (P,3,3) intrinsics, tensors or numpy, upper triangular with last row 0 0 1.
     threshold is in calibrated units (the reference's norm_thresh, e.g. 0.5 px / focal length): inlier when the Sampson error of the
@@ -205,8 +224,8 @@ def find_essential(x_A, x_B, K_A, K_B, threshold, max_iters=2000, seed=None, lo_
     entry positive; inlier mask bool).  All zeros and an empty mask when no sample gives a model, e.g. for a singular K.
     max_iters = 2000 samples of 5 points, up to 10 models each, every one scored: there is no confidence exit, so the number of
     samples is the whole budget.  At 30 % inliers (1 - 0.3^5)^2000 = 0.8 % of the calls draw no clean sample, at 40 % 1e-9; raise
-    max_iters for harder pairs."""
-    return _estimate(x_A, x_B, KIND_E, threshold, max_iters, seed, lo_iters, K_A, K_B)
+    max_iters for harder pairs.  scoring: "msac" or "magsac" (module docstring)."""
+    return _estimate(x_A, x_B, KIND_E, threshold, max_iters, seed, lo_iters, K_A, K_B, scoring=scoring)
 
 
 def recover_pose(E, x_A, x_B, K_A, K_B, mask=None):
@@ -239,24 +258,29 @@ def recover_pose(E, x_A, x_B, K_A, K_B, mask=None):
     return (R[0], t[0], out[0]) if single else (R, t, out)
 
 
-def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=2000, seed=None):
+def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=2000, seed=None, scoring="msac"):
     """Drop-in for estimate_pose of the reference (romatch/utils/utils.py:31-52) on the device: find_essential, then recover_pose on
     its inliers.  None for fewer than 5 matches, else (R, t, mask) — batched tensors for (P,N,2) input.  `conf` is accepted for the
-    signature and unused: every one of the max_iters samples is drawn and scored, there is no early stop."""
+    signature and unused: every one of the max_iters samples is drawn and scored, there is no early stop.  scoring as find_essential."""
+    _scoring(scoring)
     if kpts0.shape[-2] < 5:
         return None
-    E, mask = find_essential(kpts0, kpts1, K0, K1, norm_thresh, max_iters=max_iters, seed=seed)
+    E, mask = find_essential(kpts0, kpts1, K0, K1, norm_thresh, max_iters=max_iters, seed=seed, scoring=scoring)
     return recover_pose(E, kpts0, kpts1, K0, K1, mask)
 
 
-def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=10000, seed=None, refine_iters=0):
+def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, *, max_iters=10000, seed=None, refine_iters=0,
+                               scoring="msac"):
     """Drop-in for estimate_pose_uncalibrated of the reference (utils.py:54-76): find_fundamental with norm_thresh in PIXELS, E =
     K1^T F K0, recover_pose on the inliers of F.  None for fewer than 5 matches (find_fundamental itself needs 7).  `conf` unused.
-    refine_iters > 0: the pose comes from the F that refine_fundamental polished (see find_fundamental) and from its inliers."""
+    refine_iters > 0: the pose comes from the F that refine_fundamental polished (see find_fundamental) and from its inliers.
+    scoring as find_fundamental (the reference calls cv2.findFundamentalMat with USAC_ACCURATE here)."""
+    _scoring(scoring)
     refine_iters = _refine_iters(refine_iters)
     if kpts0.shape[-2] < 5:
         return None
-    F, mask = find_fundamental(kpts0, kpts1, threshold=norm_thresh, max_iters=max_iters, seed=seed, refine_iters=refine_iters)
+    F, mask = find_fundamental(kpts0, kpts1, threshold=norm_thresh, max_iters=max_iters, seed=seed, refine_iters=refine_iters,
+                               scoring=scoring)
     P = 1 if F.dim() == 2 else F.shape[0]
     Ka, Kb = _intrinsics(K0, P, F.device, "K0"), _intrinsics(K1, P, F.device, "K1")
     if F.dim() == 2:
@@ -389,7 +413,7 @@ def _focal(camera, name):
     return 0.5 * (fx + fy), [[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]]
 
 
-def estimate_relative_pose(kpts0, kpts1, camera0, camera1, ransac_opt=None, *, seed=None):
+def estimate_relative_pose(kpts0, kpts1, camera0, camera1, ransac_opt=None, *, seed=None, scoring="msac"):
     """Drop-in for poselib.estimate_relative_pose as the reference's PoseLib benchmark calls it, on the device: find_essential ->
     recover_pose -> refine_pose (RANSAC, cheirality, then Levenberg-Marquardt on the truncated Sampson cost of all matches).
     kpts0, kpts1: (N,2) or (P,N,2) pixel coordinates on the device; camera0, camera1: dicts with model 'PINHOLE' and params
@@ -403,7 +427,8 @@ def estimate_relative_pose(kpts0, kpts1, camera0, camera1, ransac_opt=None, *, s
       max_reproj_error    accepted (the reference passes it) and unused: it belongs to PoseLib's absolute-pose estimators
     Any other key, or another camera model, raises ValueError.  Returns (pose, info): pose.R, pose.t, pose.Rt; info = {inliers: bool
     mask of the returned pose, num_inliers: int32, model_score: fp64 truncated cost, refinements: int32 steps kept — device tensors,
-    nothing is copied to the host —, iterations: max_iterations}."""
+    nothing is copied to the host —, iterations: max_iterations}.  scoring: of find_essential; refine_pose keeps its truncated cost."""
+    _scoring(scoring)
     opt = dict(_RANSAC_OPT)
     for k, v in (ransac_opt or {}).items():
         if k not in opt:
@@ -419,7 +444,7 @@ def estimate_relative_pose(kpts0, kpts1, camera0, camera1, ransac_opt=None, *, s
     thr = float(opt["max_epipolar_error"]) * 0.5 * (1.0 / f0 + 1.0 / f1)
     K0 = torch.tensor(K0, dtype=torch.float64).to(kpts0.device)
     K1 = torch.tensor(K1, dtype=torch.float64).to(kpts0.device)
-    E, emask = find_essential(kpts0, kpts1, K0, K1, thr, max_iters=int(opt["max_iterations"]), seed=seed)
+    E, emask = find_essential(kpts0, kpts1, K0, K1, thr, max_iters=int(opt["max_iterations"]), seed=seed, scoring=scoring)
     R0, t0, mask0 = recover_pose(E, kpts0, kpts1, K0, K1, emask)
     (R, t, mask, cost, count, steps), single = _refine(R0, t0, kpts0, kpts1, K0, K1, thr, int(opt["refine_iterations"]), None)
     if single:
@@ -464,17 +489,18 @@ def minimal_samples(x_A, x_B, model="fundamental", max_iters=10000, seed=0, K_A=
     return score_hypotheses(x_A, x_B, model, 3.0, max_iters, seed, K_A, K_B)["samples"]
 
 
-def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=10000, seed=0, K_A=None, K_B=None):
+def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=10000, seed=0, K_A=None, K_B=None, *, scoring="msac"):
     """Every hypothesis of one call, before selection (batched (P,...) shapes even for a single pair):
     samples (P,iters,s) int32; models (P,iters,R,3,3) fp64 in normalised coordinates (unit Frobenius norm), R = 3 root slots
-    for F, 1 for H; valid (P,iters,R) bool; count (P,iters,R) int32 inliers; cost (P,iters,R) fp64 MSAC cost (+inf if invalid);
+    for F, 1 for H; valid (P,iters,R) bool; count (P,iters,R) int32 inliers; cost (P,iters,R) fp64 cost of the chosen `scoring`, MSAC
+    by default (+inf if invalid);
     T_A, T_B (P,3,3) fp64 normalising transforms (x_hat = T x).  A model in pixels is T_B^T F^ T_A or T_B^-1 H^ T_A.
     Pair p draws what it draws in find_fundamental / find_homography with the same seed.  An inspection helper: it keeps the
     whole batch's workspace and returns every slot, so it refuses a batch whose workspace exceeds the chunk limit of the
     estimators (192 MiB: about 35 pairs at N = 10 000 and 10 000 F samples) — call it on fewer pairs.
     model = "essential" needs K_A, K_B (as find_essential; threshold in calibrated units): R = 10 slots ordered by the solver's
     hidden variable, models in calibrated coordinates, T_A = K_A^-1, T_B = K_B^-1."""
-    kind = _kind(model)
+    kind, score = _kind(model), _scoring(scoring)
     _args(threshold, max_iters, 0)
     xa, xb, _ = _points(x_A, x_B, kind)
     P, N, iters = xa.shape[0], xa.shape[1], int(max_iters)
@@ -488,10 +514,10 @@ def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=100
         if K_A is None or K_B is None:
             raise ValueError("score_hypotheses: model 'essential' needs K_A and K_B")
         K = (_intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B"))
-        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, K)
+        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, K, score)
         T = _inverse_intrinsics(torch.stack(K, 1))
     else:
-        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws)
+        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, None, score)
         norm = _view(ws, off, 0, torch.float64, (P, 2, 4))
         T = torch.zeros((P, 2, 3, 3), dtype=torch.float64, device=xa.device)
         T[:, :, 0, 0] = norm[:, :, 2]

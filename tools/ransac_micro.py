@@ -6,6 +6,9 @@
 # recover_pose + refine_pose), at the two pose shapes; their lines give the kept steps instead of model-point evaluations.
 # refineF = refine_fundamental alone from the model of find_fundamental (seed 0), Fref = find_fundamental(refine_iters=15), at the
 # two F shapes: the extra cost of the refinement inside the estimator is Fref minus F of the same run.
+# `ransac_micro.py 10 F,H,E msac,magsac` adds the MAGSAC++ scoring: every F / H / E / pose case is then timed with each scoring named,
+# at its threshold and at the generous one of DESIGN.md §3.4 (WIDE: where MAGSAC++ is meant to be used, and where it looks up more
+# inliers), and the magsac lines end with their time over the msac time of the same case and threshold.
 import os
 import sys
 
@@ -24,9 +27,20 @@ CASES = [("F", 1, 10000, 10000, 1.5), ("F", 64, 5000, 10000, 1.5), ("H", 1, 5000
          ("refineF", 1, 10000, 10000, 1.5), ("refineF", 64, 5000, 10000, 1.5), ("Fref", 1, 10000, 10000, 1.5), ("Fref", 64, 5000, 10000, 1.5)]
 MODEL = {"F": "fundamental", "H": "homography", "E": "essential", "pose": "essential", "Fref": "fundamental"}
 CAMERA = {"model": "PINHOLE", "params": [800.0, 800.0, G.W_IMG / 2, G.H_IMG / 2]}
+WIDE = {"F": 6.0, "H": 25.0, "E": 6.0 / 800, "pose": 6.0 / 800}
+
+
+_SCENES = {}
 
 
 def scene(kind, P, N):
+    key = (kind == "H", P, N)
+    if key not in _SCENES:
+        _SCENES[key] = _scene(kind, P, N)
+    return _SCENES[key]
+
+
+def _scene(kind, P, N):
     make = G.planar_scene if kind == "H" else G.two_view_scene
     pts = [make(100 + i, N=N)[:2] for i in range(P)]
     return (torch.from_numpy(np.stack([p[0] for p in pts])).float().cuda(), torch.from_numpy(np.stack([p[1] for p in pts])).float().cuda())
@@ -35,17 +49,25 @@ def scene(kind, P, N):
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
     kinds = sys.argv[2].split(",") if len(sys.argv) > 2 else ["F", "H", "E", "pose", "refine", "relpose", "refineF", "Fref"]
+    scorings = sys.argv[3].split(",") if len(sys.argv) > 3 else ["msac"]
     K = torch.from_numpy(PR.K_SCENE).cuda()
-    for kind, P, N, iters, thr in CASES:
+    runs = [(c, "msac", c[4]) for c in CASES]
+    if scorings != ["msac"]:
+        runs = [(c, sc, thr) for c in CASES for thr in ((c[4], WIDE[c[0]]) if c[0] in WIDE else (c[4],))
+                for sc in (scorings if c[0] in WIDE else ["msac"])]
+    base = {}
+    for (kind, P, N, iters, _), scoring, thr in runs:
         if kind not in kinds:
             continue
         xa, xb = scene(kind, P, N)
+        score = {} if scoring == "msac" else {"scoring": scoring}
+        label = kind if scoring == "msac" and scorings == ["msac"] else f"{kind}/{scoring} thr={thr:.4g}"
         if kind == "E":
             def fn(a, b, threshold, max_iters, seed):
-                return geometry.find_essential(a, b, K, K, threshold, max_iters=max_iters, seed=seed)
+                return geometry.find_essential(a, b, K, K, threshold, max_iters=max_iters, seed=seed, **score)
         elif kind == "pose":
             def fn(a, b, threshold, max_iters, seed):
-                return geometry.estimate_pose(a, b, K, K, threshold, max_iters=max_iters, seed=seed)
+                return geometry.estimate_pose(a, b, K, K, threshold, max_iters=max_iters, seed=seed, **score)
         elif kind == "refine":
             R0, t0, _ = geometry.estimate_pose(xa, xb, K, K, thr, max_iters=iters, seed=0)
 
@@ -64,7 +86,9 @@ def main():
             def fn(a, b, threshold, max_iters, seed):
                 return geometry.find_fundamental(a, b, threshold=threshold, max_iters=max_iters, seed=seed, refine_iters=15)
         else:
-            fn = geometry.find_fundamental if kind == "F" else geometry.find_homography
+            def fn(a, b, threshold, max_iters, seed):
+                return (geometry.find_fundamental if kind == "F" else geometry.find_homography)(a, b, threshold=threshold,
+                                                                                                max_iters=max_iters, seed=seed, **score)
         for _ in range(3):
             fn(xa, xb, threshold=thr, max_iters=iters, seed=0)
         torch.cuda.synchronize()
@@ -88,9 +112,12 @@ def main():
         valid = sum(int(geometry.score_hypotheses(xa[a:a + 16], xb[a:a + 16], MODEL[kind], thr, iters, seed=0, **extra)["valid"].sum())
                     for a in range(0, P, 16))
         evals = valid * N
-        print(f"{kind:4s} P={P:3d} N={N:5d} iters={iters:5d}: {ms:8.3f} ms/call (median of {reps}, min {min(times):.3f})  "
+        if scoring == "msac":
+            base[(kind, P, thr)] = ms
+        ratio = f"  {ms / base[(kind, P, thr)]:.2f} x msac" if scoring != "msac" and (kind, P, thr) in base else ""
+        print(f"{label:4s} P={P:3d} N={N:5d} iters={iters:5d}: {ms:8.3f} ms/call (median of {reps}, min {min(times):.3f})  "
               f"{ms / P:7.3f} ms/pair  {evals / (ms * 1e-3):.3e} model-point evaluations/s  ({evals:.3e} evaluations, "
-              f"{valid} valid models)")
+              f"{valid} valid models){ratio}")
 
 
 if __name__ == "__main__":
