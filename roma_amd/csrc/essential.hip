@@ -41,6 +41,10 @@
 // Pose recovery: eigen-decomposition of E^T E (Jacobi) -> v1, v2, v3 = v1 x v2; u1 = E v1 / |E v1|, u2 = E v2 made orthogonal to u1,
 // u3 = u1 x u2; R = U W V^T or U W^T V^T, t = +-u3, candidates in the order (W,+) (W,-) (W^T,+) (W^T,-).  Depths of a match under
 // a candidate from the normal equations of lambda_B x_B = lambda_A R x_A + t; a match votes when both are finite and positive.
+//
+// Shared code: the scoring, the workspace layout and the checks are ransac_common.h's (with geometry.hip); elimination, jacobi_lds
+// and invert_k are twoview_math.h's.  Steps 1 and 2 of essential_select_kernel repeat geometry.hip's select_kernel, statement for
+// statement.
 #include "ransac_common.h"
 
 namespace roma {
@@ -829,32 +833,23 @@ __global__ __launch_bounds__(256) void recover_pose_kernel(const double* __restr
 }
 
 // --------------------------------------------------------------------------------------------------------------- workspace
-constexpr int WE_NORM = 0, WE_PTS = 1, WE_SAMPLES = 2, WE_MODELS = 3, WE_VALID = 4, WE_SLAB_COST = 5, WE_SLAB_CNT = 6, WE_COST = 7,
-              WE_COUNT = 8, WE_XH = 9, WE_N = 10;
+// ransac_common.h's regions, then the calibrated points xh
+constexpr int WE_XH = WS_N, WE_N = WS_N + 1;
 
 long layout_e(int P, int N, int iters, long* off) {
-  const long M = (long)iters * E_R, C = (N + CHUNK - 1) / CHUNK;
-  const long bytes[WE_N] = {(long)P * 8 * 8, (long)P * N * 16, (long)P * iters * E_S * 4, (long)P * M * 72, (long)P * M * 4,
-                            (long)P * C * M * 4, (long)P * C * M * 4, (long)P * M * 8, (long)P * M * 4, (long)P * N * 32};
-  long o = 0;
-  for (int i = 0; i < WE_N; ++i) {
-    if (off) off[i] = o;
-    o += (bytes[i] + 255) / 256 * 256;
-  }
-  return o;
+  const long xh_bytes = (long)P * N * 32;
+  return ws_layout(E_S, E_R, P, N, iters, &xh_bytes, 1, off);
 }
 
 int check_args_e(const char* fn, const void* xa, const void* xb, const void* Ka, const void* Kb, const void* ws, int P, int N,
                  int iters, float threshold, long ws_bytes) {
   ROMA_REQUIRE(xa && xb && Ka && Kb && ws, ROMA_E_ARG, "%s: null pointer", fn);
-  ROMA_REQUIRE(P >= 1 && P <= 65535 && iters >= 1 && iters <= (1 << 24), ROMA_E_SHAPE, "%s: bad shape P=%d iters=%d", fn, P, iters);
-  ROMA_REQUIRE(N >= E_S && N <= (1 << 26), ROMA_E_SHAPE, "%s: N=%d matches, need at least %d for the minimal sample", fn, N, E_S);
+  const int rc = check_shape(fn, P, N, iters, E_S);
+  if (rc) return rc;
   ROMA_REQUIRE(((long)P * iters + GROUPS - 1) / GROUPS <= 0x7FFFFFFFL, ROMA_E_SHAPE, "%s: P * iters = %ld samples in one call", fn,
                (long)P * iters);
   ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
-  ROMA_REQUIRE(ws_bytes >= layout_e(P, N, iters, nullptr), ROMA_E_ARG, "%s: workspace of %ld bytes, need %ld", fn, ws_bytes,
-               layout_e(P, N, iters, nullptr));
-  return 0;
+  return check_workspace(fn, ws_bytes, layout_e(P, N, iters, nullptr));
 }
 
 }  // namespace
@@ -882,15 +877,15 @@ int essential_hypotheses(const char* fn, const double* xa, const double* xb, con
   long off[WE_N];
   layout_e(P, N, iters, off);
   char* w = static_cast<char*>(ws);
-  double* norm = (double*)(w + off[WE_NORM]);
-  float* pts = (float*)(w + off[WE_PTS]);
-  int* samples = (int*)(w + off[WE_SAMPLES]);
-  double* models = (double*)(w + off[WE_MODELS]);
-  int* valid = (int*)(w + off[WE_VALID]);
-  float* slab_cost = (float*)(w + off[WE_SLAB_COST]);
-  int* slab_cnt = (int*)(w + off[WE_SLAB_CNT]);
-  double* cost = (double*)(w + off[WE_COST]);
-  int* count = (int*)(w + off[WE_COUNT]);
+  double* norm = (double*)(w + off[WS_NORM]);
+  float* pts = (float*)(w + off[WS_PTS]);
+  int* samples = (int*)(w + off[WS_SAMPLES]);
+  double* models = (double*)(w + off[WS_MODELS]);
+  int* valid = (int*)(w + off[WS_VALID]);
+  float* slab_cost = (float*)(w + off[WS_SLAB_COST]);
+  int* slab_cnt = (int*)(w + off[WS_SLAB_CNT]);
+  double* cost = (double*)(w + off[WS_COST]);
+  int* count = (int*)(w + off[WS_COUNT]);
   double* xh = (double*)(w + off[WE_XH]);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int M = iters * E_R, C = (N + CHUNK - 1) / CHUNK;
@@ -926,7 +921,7 @@ int essential_select(const char* fn, const double* xa, const double* xb, const d
   auto sel = essential_select_kernel<SCORE_MSAC>;
   if (scoring == SCORE_MAGSAC) sel = essential_select_kernel<SCORE_MAGSAC>;
   hipLaunchKernelGGL(sel, dim3(P), dim3(256), 0, static_cast<hipStream_t>(stream), (const double*)(w + off[WE_XH]),
-                     (const float4*)(w + off[WE_PTS]), (const double*)(w + off[WE_MODELS]), (const double*)(w + off[WE_COST]), N,
+                     (const float4*)(w + off[WS_PTS]), (const double*)(w + off[WS_MODELS]), (const double*)(w + off[WS_COST]), N,
                      iters * E_R, threshold * threshold, lo_iters, E, mask);
   return check_launch(fn);
 }

@@ -34,7 +34,12 @@
 //               not finite or has no second singular value (sigma_2^2 <= 1e-14 sigma_1^2: the eigenvalues of F^^T F^ carry an
 //               absolute error of a few eps sigma_1^2, below that v_2 is not determined): the input is returned bit for bit, with
 //               its own mask, cost and count, and steps = 0
-#include "ransac_common.h"
+//
+// Shared with pose_refine.hip, in twoview_math.h: the residual, Match, block_sum, solve_step and the checks of the entry point; with
+// geometry.hip's select_kernel: Norm, to_pixels, jacobi_lds.  The schedules stay apart: here a candidate gets a cost pass, and
+// only a kept step a Jacobian pass.  The row of the normal equations and the mask loop are written out here as in pose_refine.hip:
+// this kernel sits at 256 VGPRs, and behind a shared function the compiler allocates its registers differently.
+#include "twoview_math.h"
 
 namespace roma {
 namespace {
@@ -45,46 +50,14 @@ constexpr int RF_COST = 35, RF_COUNT = 36;
 constexpr int RF_MIN_MATCHES = 8;
 constexpr double RF_LAMBDA0 = 1e-3, RF_LAMBDA_MIN = 1e-10, RF_ACCEPT_REL = 1e-12, RF_RANK_TOL = 1e-14;
 
-struct Norm {
-  double cxA, cyA, sA, cxB, cyB, sB;
-};
-
-struct PixelMatch {
-  double x, y, u, v;
-  bool ok;
-};
-
 // match q in pixels; ok: finite and allowed by mask_in
-__device__ __forceinline__ PixelMatch load_pixels(const double2* __restrict__ xa, const double2* __restrict__ xb,
-                                                  const unsigned char* mask_in, size_t q) {
+__device__ __forceinline__ Match load_pixels(const double2* __restrict__ xa, const double2* __restrict__ xb,
+                                             const unsigned char* mask_in, size_t q) {
   const double2 a = xa[q], b = xb[q];
-  PixelMatch m;
+  Match m;
   m.x = a.x; m.y = a.y; m.u = b.x; m.v = b.y;
   m.ok = isfinite(a.x) && isfinite(a.y) && isfinite(b.x) && isfinite(b.y) && (!mask_in || mask_in[q] != 0);
   return m;
-}
-
-// the K sums of every thread reduced in a fixed order: on return every thread holds the same s[]
-template <int K> __device__ __forceinline__ void block_sum(double (&s)[K], double (*red)[RF_NSUM]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[wave][k] = s[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double acc = red[0][k];
-#pragma unroll
-    for (int w = 1; w < RF_WAVES; ++w) acc += red[w][k];
-    s[k] = acc;
-  }
-  __syncthreads();
 }
 
 // Hartley normalisation of both images over the usable matches (geometry.hip's normalize_kernel, with the mask)
@@ -92,46 +65,29 @@ __device__ __forceinline__ Norm normalisation(const double2* __restrict__ xa, co
                                               size_t base, int N, double (*red)[RF_NSUM]) {
   double c[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   for (int i = threadIdx.x; i < N; i += RF_THREADS) {
-    const PixelMatch m = load_pixels(xa, xb, mask_in, base + i);
+    const Match m = load_pixels(xa, xb, mask_in, base + i);
     if (m.ok) { c[0] += m.x; c[1] += m.y; c[2] += m.u; c[3] += m.v; c[4] += 1.0; }
   }
-  block_sum<5>(c, red);
+  block_sum<5, RF_WAVES>(c, red);
   const double cnt = c[4], inv = cnt > 0.0 ? 1.0 / cnt : 0.0;
   Norm n;
   n.cxA = c[0] * inv; n.cyA = c[1] * inv; n.cxB = c[2] * inv; n.cyB = c[3] * inv;
   double d[2] = {0.0, 0.0};
   for (int i = threadIdx.x; i < N; i += RF_THREADS) {
-    const PixelMatch m = load_pixels(xa, xb, mask_in, base + i);
+    const Match m = load_pixels(xa, xb, mask_in, base + i);
     if (m.ok) {
       const double ax = m.x - n.cxA, ay = m.y - n.cyA, bx = m.u - n.cxB, by = m.v - n.cyB;
       d[0] += sqrt(ax * ax + ay * ay);
       d[1] += sqrt(bx * bx + by * by);
     }
   }
-  block_sum<2>(d, red);
+  block_sum<2, RF_WAVES>(d, red);
   const double mdA = d[0] * inv, mdB = d[1] * inv;
   n.sA = 1.4142135623730951 / mdA;
   n.sB = 1.4142135623730951 / mdB;
   if (!(mdA > 0.0) || !isfinite(n.sA)) n.sA = 1.0;
   if (!(mdB > 0.0) || !isfinite(n.sB)) n.sB = 1.0;
   return n;
-}
-
-// o = T_B^T c T_A: pixels from normalised coordinates (select_kernel's de-normalisation)
-__device__ __forceinline__ void to_pixels(const double* c, const Norm& n, double* o) {
-  double g[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    g[3 * r] = c[3 * r] * n.sA;
-    g[3 * r + 1] = c[3 * r + 1] * n.sA;
-    g[3 * r + 2] = c[3 * r + 2] - n.sA * (n.cxA * c[3 * r] + n.cyA * c[3 * r + 1]);
-  }
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    o[j] = n.sB * g[j];
-    o[3 + j] = n.sB * g[3 + j];
-    o[6 + j] = g[6 + j] - n.sB * (n.cxB * g[j] + n.cyB * g[3 + j]);
-  }
 }
 
 // o = T_B^-T f T_A^-1: normalised coordinates from pixels
@@ -214,7 +170,7 @@ __device__ __forceinline__ void cost_pass(const double* f, const double2* __rest
                                           double& cost, double& count) {
   double c[2] = {0.0, 0.0};
   for (int i = threadIdx.x; i < N; i += RF_THREADS) {
-    const PixelMatch m = load_pixels(xa, xb, mask_in, base + i);
+    const Match m = load_pixels(xa, xb, mask_in, base + i);
     double ex[3], et[2], n, d, isd, r;
     apply_model(f, m.x, m.y, m.u, m.v, ex, et);
     sampson_terms(ex, et, m.u, m.v, n, d);
@@ -223,7 +179,7 @@ __device__ __forceinline__ void cost_pass(const double* f, const double2* __rest
     c[0] += m.ok ? (in ? r2 : t2) : 0.0;
     c[1] += in ? 1.0 : 0.0;
   }
-  block_sum<2>(c, red);
+  block_sum<2, RF_WAVES>(c, red);
   cost = c[0];
   count = c[1];
 }
@@ -237,7 +193,7 @@ __device__ __forceinline__ void jacobian_pass(const double* M, const double2* __
   for (int i = threadIdx.x; i < N; i += RF_THREADS) {
     // M is read from LDS for every match (broadcast reads): hoisted out of the loop its 72 values would take 144 registers
     asm volatile("" ::: "memory");
-    const PixelMatch m = load_pixels(xa, xb, mask_in, base + i);
+    const Match m = load_pixels(xa, xb, mask_in, base + i);
     double ex[3], et[2], n, d, isd, r;
     apply_model(M, m.x, m.y, m.u, m.v, ex, et);
     sampson_terms(ex, et, m.u, m.v, n, d);
@@ -264,53 +220,7 @@ __device__ __forceinline__ void jacobian_pass(const double* M, const double2* __
     s[RF_COST] += m.ok ? (in ? r2 : t2) : 0.0;
     s[RF_COUNT] += in ? 1.0 : 0.0;
   }
-  block_sum<RF_NSUM>(s, red);
-}
-
-// delta of (A + lambda diag A) delta = -g, A and g from the sums; false on a pivot that is not positive (NaN included)
-__device__ __forceinline__ bool solve_step(const double (&s)[RF_NSUM], double lambda, double (&delta)[RF_NPAR]) {
-  double L[RF_NPAR][RF_NPAR];
-  int o = 0;
-#pragma unroll
-  for (int a = 0; a < RF_NPAR; ++a)
-#pragma unroll
-    for (int b = a; b < RF_NPAR; ++b) {
-      const double v = s[o++];
-      L[b][a] = a == b ? v + lambda * v : v;               // lower triangle, overwritten by the factor
-    }
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < RF_NPAR; ++j) {
-    double p = L[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) p -= L[j][k] * L[j][k];
-    ok = ok && p > 0.0 && isfinite(p);
-    const double dj = sqrt(p), inv = 1.0 / dj;
-    L[j][j] = dj;
-#pragma unroll
-    for (int i = j + 1; i < RF_NPAR; ++i) {
-      double v = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-      L[i][j] = v * inv;
-    }
-  }
-  double y[RF_NPAR];
-#pragma unroll
-  for (int i = 0; i < RF_NPAR; ++i) {
-    double v = -s[RF_NTRI + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-    y[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = RF_NPAR - 1; i >= 0; --i) {
-    double v = y[i];
-#pragma unroll
-    for (int k = i + 1; k < RF_NPAR; ++k) v -= L[k][i] * delta[k];
-    delta[i] = v / L[i][i];
-  }
-  return ok;
+  block_sum<RF_NSUM, RF_WAVES>(s, red);
 }
 
 // Xc = X exp([w]x), |w| limited to 1 rad: every row a of X becomes a + A (a x w) + B ((a x w) x w)
@@ -419,7 +329,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_fundamental_kernel(const do
         need_jacobian = false;
       }
       double delta[RF_NPAR];
-      if (!solve_step(sums, lambda, delta)) { failed = true; break; }
+      if (!solve_step<RF_NPAR>(sums, sums + RF_NTRI, lambda, delta)) { failed = true; break; }
       rotate_right(U, delta, series, Uc);
       rotate_right(V, delta + 3, series, Vc);
       sc = s + delta[6];
@@ -466,7 +376,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_fundamental_kernel(const do
   }
   // the mask of the returned model: the r^2 of the pass that counted its inliers, bit for bit
   for (int i = tid; i < N; i += RF_THREADS) {
-    const PixelMatch m = load_pixels(xa, xb, mask_in, base + i);
+    const Match m = load_pixels(xa, xb, mask_in, base + i);
     double ex[3], et[2], n, d, isd, r;
     apply_model(fk, m.x, m.y, m.u, m.v, ex, et);
     sampson_terms(ex, et, m.u, m.v, n, d);
@@ -483,12 +393,8 @@ extern "C" int roma_refine_fundamental(const double* xa, const double* xb, const
                                        double threshold, int iters, double* F, unsigned char* mask, double* cost, int* count,
                                        int* steps, void* stream) {
   ROMA_REQUIRE(xa && xb && F_in && F && mask && cost && count && steps, ROMA_E_ARG, "roma_refine_fundamental: null pointer");
-  ROMA_REQUIRE(P >= 1 && P <= (1 << 24), ROMA_E_SHAPE, "roma_refine_fundamental: bad shape P=%d", P);
-  ROMA_REQUIRE(N >= RF_MIN_MATCHES && N <= (1 << 26), ROMA_E_SHAPE, "roma_refine_fundamental: N=%d matches, need at least %d", N,
-               RF_MIN_MATCHES);
-  ROMA_REQUIRE(threshold > 0.0 && threshold < 1e18, ROMA_E_ARG, "roma_refine_fundamental: threshold must be positive, got %g", threshold);
-  ROMA_REQUIRE(iters >= 0 && iters <= (1 << 16), ROMA_E_ARG, "roma_refine_fundamental: iters must be in [0, 65536], got %d", iters);
-  ROMA_REQUIRE(aligned16(xa) && aligned16(xb), ROMA_E_ALIGN, "roma_refine_fundamental: xa and xb must be 16-byte aligned");
+  const int rc = check_refine(__func__, xa, xb, P, N, RF_MIN_MATCHES, threshold, iters);
+  if (rc) return rc;
   hipLaunchKernelGGL(refine_fundamental_kernel, dim3(P), dim3(RF_THREADS), 0, static_cast<hipStream_t>(stream), (const double2*)xa,
                      (const double2*)xb, F_in, mask_in, N, threshold * threshold, iters, F, mask, cost, count, steps);
   ROMA_CHECK_LAUNCH();

@@ -25,6 +25,10 @@
 // Rank test of the minimal systems: Gaussian elimination with partial pivoting; a pivot with |pivot| <= 1e-10 * (largest
 // |entry| of the system) rejects the sample.  H samples are also rejected when any 3 of the 4 points are collinear in either
 // image: |(b - a) x (c - a)| <= 1e-6 |b - a| |c - a| (normalised coordinates).
+//
+// Shared code: ransac_common.h has the scoring (score_kernel, reduce_kernel, block_score), the workspace layout and the checks
+// that essential.hip uses too; twoview_math.h the fp64 helpers (elimination, jacobi_lds, Norm / to_pixels) that the refinement
+// kernels use as well.  Steps 1 and 2 of select_kernel are repeated in essential_select_kernel, statement for statement.
 #include "ransac_common.h"
 
 namespace roma {
@@ -332,7 +336,7 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
 
   // 2. local optimisation: least-squares refit on the inliers (SCORE_MAGSAC: weighted by W under the current model, the rows scaled
   // by sqrt W), kept only if its cost is lower
-  const double cxA = nrm[0], cyA = nrm[1], sA = nrm[2], cxB = nrm[4], cyB = nrm[5], sB = nrm[6];
+  const Norm nm{nrm[0], nrm[1], nrm[2], nrm[4], nrm[5], nrm[6]};
   for (int round = 0; round < lo_iters; ++round) {
     if (cn < Kind<KIND>::LO_MIN) break;
     float m[9];
@@ -345,7 +349,8 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
       const float e = point_error<KIND>(m, pq[i], ka, kb);
       if (!(e < t2)) continue;
       const size_t q = ((size_t)p * N + i) * 2;
-      const double x = (xa[q] - cxA) * sA, y = (xa[q + 1] - cyA) * sA, u = (xb[q] - cxB) * sB, v = (xb[q + 1] - cyB) * sB;
+      const double x = (xa[q] - nm.cxA) * nm.sA, y = (xa[q + 1] - nm.cyA) * nm.sA, u = (xb[q] - nm.cxB) * nm.sB,
+                   v = (xb[q + 1] - nm.cyB) * nm.sB;
       double sw = 1.0;
       if constexpr (SCORE == SCORE_MAGSAC) sw = sqrt((double)magsac_lookup(magsac_weight_cells, e, (float)MAGSAC_CELLS / t2));
       if constexpr (KIND == KIND_F) {
@@ -438,23 +443,9 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
 
   // 3. de-normalise (F = T_B^T F^ T_A, H = T_B^-1 H^ T_A), fix scale and sign; mask from the final model
   if (tid == 0) {
-    double g[9], o[9];
-    const double* c = cur;
+    double o[9];
     if constexpr (KIND == KIND_F) {
-      // F^ T_A: columns 0,1 scaled by sA, column 2 = -sA (cA . cols 0,1) + col 2
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        g[3 * r] = c[3 * r] * sA;
-        g[3 * r + 1] = c[3 * r + 1] * sA;
-        g[3 * r + 2] = c[3 * r + 2] - sA * (cxA * c[3 * r] + cyA * c[3 * r + 1]);
-      }
-      // T_B^T G: rows 0,1 scaled by sB, row 2 = -sB (cB . rows 0,1) + row 2
-#pragma unroll
-      for (int cc2 = 0; cc2 < 3; ++cc2) {
-        o[cc2] = sB * g[cc2];
-        o[3 + cc2] = sB * g[3 + cc2];
-        o[6 + cc2] = g[6 + cc2] - sB * (cxB * g[cc2] + cyB * g[3 + cc2]);
-      }
+      to_pixels(cur, nm, o);
       unit_frobenius(o);
       int jm = 0;
 #pragma unroll
@@ -467,17 +458,13 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
 #pragma unroll
       for (int i = 0; i < 9; ++i) o[i] *= sgn;
     } else {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        g[3 * r] = c[3 * r] * sA;
-        g[3 * r + 1] = c[3 * r + 1] * sA;
-        g[3 * r + 2] = c[3 * r + 2] - sA * (cxA * c[3 * r] + cyA * c[3 * r + 1]);
-      }
+      double g[9];
+      times_t_a(cur, nm, g);
       // T_B^-1 G: rows 0,1 = row / sB + cB * row 2
 #pragma unroll
       for (int cc2 = 0; cc2 < 3; ++cc2) {
-        o[cc2] = g[cc2] / sB + cxB * g[6 + cc2];
-        o[3 + cc2] = g[3 + cc2] / sB + cyB * g[6 + cc2];
+        o[cc2] = g[cc2] / nm.sB + nm.cxB * g[6 + cc2];
+        o[3 + cc2] = g[3 + cc2] / nm.sB + nm.cyB * g[6 + cc2];
         o[6 + cc2] = g[6 + cc2];
       }
       double fro = 0.0;
@@ -503,30 +490,15 @@ __global__ __launch_bounds__(256) void select_kernel(const double* __restrict__ 
 }
 
 // --------------------------------------------------------------------------------------------------------------- workspace
-constexpr int WS_NORM = 0, WS_PTS = 1, WS_SAMPLES = 2, WS_MODELS = 3, WS_VALID = 4, WS_SLAB_COST = 5, WS_SLAB_CNT = 6,
-              WS_COST = 7, WS_COUNT = 8, WS_N = 9;
-
 long layout(int kind, int P, int N, int iters, long* off) {
-  const long S = kind == KIND_F ? 7 : 4, R = kind == KIND_F ? 3 : 1, M = (long)iters * R, C = (N + CHUNK - 1) / CHUNK;
-  const long bytes[WS_N] = {(long)P * 8 * 8, (long)P * N * 16, (long)P * iters * S * 4, (long)P * M * 72, (long)P * M * 4,
-                            (long)P * C * M * 4, (long)P * C * M * 4, (long)P * M * 8, (long)P * M * 4};
-  long o = 0;
-  for (int i = 0; i < WS_N; ++i) {
-    if (off) off[i] = o;
-    o += (bytes[i] + 255) / 256 * 256;
-  }
-  return o;
+  return ws_layout(kind == KIND_F ? 7 : 4, kind == KIND_F ? 3 : 1, P, N, iters, nullptr, 0, off);
 }
 
 int check_args(const char* fn, int kind, const void* xa, const void* xb, const void* ws, int P, int N, int iters, long ws_bytes) {
   ROMA_REQUIRE(xa && xb && ws, ROMA_E_ARG, "%s: null pointer", fn);
   ROMA_REQUIRE(kind == KIND_F || kind == KIND_H, ROMA_E_ARG, "%s: kind must be 0 (fundamental) or 1 (homography), got %d", fn, kind);
-  const int smin = kind == KIND_F ? 7 : 4;
-  ROMA_REQUIRE(P >= 1 && P <= 65535 && iters >= 1 && iters <= (1 << 24), ROMA_E_SHAPE, "%s: bad shape P=%d iters=%d", fn, P, iters);
-  ROMA_REQUIRE(N >= smin && N <= (1 << 26), ROMA_E_SHAPE, "%s: N=%d matches, need at least %d for the minimal sample", fn, N, smin);
-  ROMA_REQUIRE(ws_bytes >= layout(kind, P, N, iters, nullptr), ROMA_E_ARG, "%s: workspace of %ld bytes, need %ld", fn, ws_bytes,
-               layout(kind, P, N, iters, nullptr));
-  return 0;
+  const int rc = check_shape(fn, P, N, iters, kind == KIND_F ? 7 : 4);
+  return rc ? rc : check_workspace(fn, ws_bytes, layout(kind, P, N, iters, nullptr));
 }
 
 }  // namespace

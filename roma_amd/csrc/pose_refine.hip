@@ -27,13 +27,19 @@
 //               bit of the pose ends the schedule (no later one would)
 //   failure     fewer than 5 weighted matches under the input pose, a Cholesky pivot that is not positive, an input pose that is
 //               not finite or has t = 0: the input pose is returned as it came, with its own mask, cost and count
-#include "ransac_common.h"
+//
+// Shared with fundamental_refine.hip, in twoview_math.h: the residual, Match, block_sum, solve_step and the checks of the entry
+// point.  The schedules stay apart: here one pass gives the cost and the normal equations of a candidate.  The row of the normal
+// equations and the mask loop are written out here as in fundamental_refine.hip: this kernel sits at 256 VGPRs, and behind a shared
+// function the compiler allocates its registers differently.
+#include "twoview_math.h"
 
 namespace roma {
 namespace {
 
 constexpr int RP_THREADS = 256, RP_WAVES = RP_THREADS / 64;
-constexpr int RP_NPAR = 5, RP_NSUM = 22;                      // 15 + 5 + cost + count
+constexpr int RP_NPAR = 5, RP_NTRI = 15, RP_NSUM = 22;        // 15 + 5 + cost + count
+constexpr int RP_COST = 20, RP_COUNT = 21;
 constexpr int RP_MIN_MATCHES = 5;
 constexpr double RP_LAMBDA0 = 1e-3, RP_LAMBDA_MIN = 1e-10, RP_ACCEPT_REL = 1e-12;
 
@@ -73,11 +79,6 @@ __device__ __forceinline__ void model_matrices(const double* R, const double* t,
   skew_mul(b1, R, M[4]);
   skew_mul(b2, R, M[5]);
 }
-
-struct Match {
-  double x, y, u, v;
-  bool ok;
-};
 
 // the calibrated match i of pair p, as calibrate_kernel computes it; ok: finite and allowed by mask_in
 __device__ __forceinline__ Match load_match(const double2* __restrict__ xa, const double2* __restrict__ xb, const unsigned char* mask_in,
@@ -125,75 +126,11 @@ __device__ __forceinline__ void evaluate(const double* R, const double* t, const
 #pragma unroll
       for (int b = a; b < RP_NPAR; ++b, ++o) s[o] = __builtin_fma(J[a], J[b], s[o]);
 #pragma unroll
-    for (int a = 0; a < RP_NPAR; ++a) s[15 + a] = __builtin_fma(J[a], rw, s[15 + a]);
-    s[20] += m.ok ? (in ? r2 : t2) : 0.0;
-    s[21] += in ? 1.0 : 0.0;
+    for (int a = 0; a < RP_NPAR; ++a) s[RP_NTRI + a] = __builtin_fma(J[a], rw, s[RP_NTRI + a]);
+    s[RP_COST] += m.ok ? (in ? r2 : t2) : 0.0;
+    s[RP_COUNT] += in ? 1.0 : 0.0;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < RP_NSUM; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < RP_NSUM; ++k) red[wave][k] = s[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < RP_NSUM; ++k) {
-    double acc = red[0][k];
-#pragma unroll
-    for (int w = 1; w < RP_WAVES; ++w) acc += red[w][k];
-    s[k] = acc;
-  }
-  __syncthreads();
-}
-
-// delta of (A + lambda diag A) delta = -g, A and g from the sums; false on a pivot that is not positive (NaN included)
-__device__ __forceinline__ bool solve_step(const double (&s)[RP_NSUM], double lambda, double (&delta)[RP_NPAR]) {
-  double L[RP_NPAR][RP_NPAR];
-  int o = 0;
-#pragma unroll
-  for (int a = 0; a < RP_NPAR; ++a)
-#pragma unroll
-    for (int b = a; b < RP_NPAR; ++b) {
-      const double v = s[o++];
-      L[b][a] = a == b ? v + lambda * v : v;               // lower triangle, overwritten by the factor
-    }
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < RP_NPAR; ++j) {
-    double p = L[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) p -= L[j][k] * L[j][k];
-    ok = ok && p > 0.0 && isfinite(p);
-    const double dj = sqrt(p), inv = 1.0 / dj;
-    L[j][j] = dj;
-#pragma unroll
-    for (int i = j + 1; i < RP_NPAR; ++i) {
-      double v = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-      L[i][j] = v * inv;
-    }
-  }
-  double y[RP_NPAR];
-#pragma unroll
-  for (int i = 0; i < RP_NPAR; ++i) {
-    double v = -s[15 + i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-    y[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = RP_NPAR - 1; i >= 0; --i) {
-    double v = y[i];
-#pragma unroll
-    for (int k = i + 1; k < RP_NPAR; ++k) v -= L[k][i] * delta[k];
-    delta[i] = v / L[i][i];
-  }
-  return ok;
+  block_sum<RP_NSUM, RP_WAVES>(s, red);
 }
 
 // Rc = orthonormalised exp([w]x) R, tc = (t + a b1 + b b2) / |.|
@@ -273,7 +210,7 @@ __global__ __launch_bounds__(RP_THREADS) void refine_pose_kernel(const double2* 
       for (int i = 0; i < 3; ++i) tc[i] = t[i];
     } else {
       double delta[RP_NPAR];
-      if (!solve_step(s, lambda, delta)) { failed = true; break; }
+      if (!solve_step<RP_NPAR>(s, s + RP_NTRI, lambda, delta)) { failed = true; break; }
       apply_step(Rk, tk, delta, Rc, tc);
       bool moved = false;
 #pragma unroll
@@ -284,8 +221,8 @@ __global__ __launch_bounds__(RP_THREADS) void refine_pose_kernel(const double2* 
     }
     evaluate(Rc, tc, xa, xb, mask_in, base, N, ia, ib, kok, t2, red, sc);
     const bool first = it == 0;
-    if (first) { cost0 = sc[20]; count0 = sc[21]; }
-    if (first || sc[20] < s[20] * (1.0 - RP_ACCEPT_REL)) {
+    if (first) { cost0 = sc[RP_COST]; count0 = sc[RP_COUNT]; }
+    if (first || sc[RP_COST] < s[RP_COST] * (1.0 - RP_ACCEPT_REL)) {
 #pragma unroll
       for (int i = 0; i < 9; ++i) Rk[i] = Rc[i];
 #pragma unroll
@@ -303,8 +240,8 @@ __global__ __launch_bounds__(RP_THREADS) void refine_pose_kernel(const double2* 
   }
   if (failed) {                                             // the input pose, as it came
     steps = 0;
-    s[20] = cost0;
-    s[21] = count0;
+    s[RP_COST] = cost0;
+    s[RP_COUNT] = count0;
   } else {
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = Rk[i];
@@ -314,11 +251,10 @@ __global__ __launch_bounds__(RP_THREADS) void refine_pose_kernel(const double2* 
   if (tid < 9) R_out[p * 9 + tid] = R[tid];
   if (tid < 3) t_out[p * 3 + tid] = t[tid];
   if (tid == 0) {
-    cost_out[p] = s[20];
-    count_out[p] = (int)s[21];
+    cost_out[p] = s[RP_COST];
+    count_out[p] = (int)s[RP_COUNT];
     steps_out[p] = steps;
   }
-  // the mask of the returned pose: the r^2 of the pass that counted its inliers, bit for bit
   double M[6][9];
   model_matrices(R, t, M);
   for (int i = tid; i < N; i += RP_THREADS) {
@@ -340,11 +276,8 @@ extern "C" int roma_refine_pose(const double* xa, const double* xb, const double
                                 double* t, unsigned char* mask, double* cost, int* count, int* steps, void* stream) {
   ROMA_REQUIRE(xa && xb && Ka && Kb && R_in && t_in && R && t && mask && cost && count && steps, ROMA_E_ARG,
                "roma_refine_pose: null pointer");
-  ROMA_REQUIRE(P >= 1 && P <= (1 << 24), ROMA_E_SHAPE, "roma_refine_pose: bad shape P=%d", P);
-  ROMA_REQUIRE(N >= RP_MIN_MATCHES && N <= (1 << 26), ROMA_E_SHAPE, "roma_refine_pose: N=%d matches, need at least %d", N, RP_MIN_MATCHES);
-  ROMA_REQUIRE(threshold > 0.0 && threshold < 1e18, ROMA_E_ARG, "roma_refine_pose: threshold must be positive, got %g", threshold);
-  ROMA_REQUIRE(iters >= 0 && iters <= (1 << 16), ROMA_E_ARG, "roma_refine_pose: iters must be in [0, 65536], got %d", iters);
-  ROMA_REQUIRE(aligned16(xa) && aligned16(xb), ROMA_E_ALIGN, "roma_refine_pose: xa and xb must be 16-byte aligned");
+  const int rc = check_refine(__func__, xa, xb, P, N, RP_MIN_MATCHES, threshold, iters);
+  if (rc) return rc;
   hipLaunchKernelGGL(refine_pose_kernel, dim3(P), dim3(RP_THREADS), 0, static_cast<hipStream_t>(stream), (const double2*)xa,
                      (const double2*)xb, Ka, Kb, R_in, t_in, mask_in, N, threshold * threshold, iters, R, t, mask, cost, count, steps);
   ROMA_CHECK_LAUNCH();
