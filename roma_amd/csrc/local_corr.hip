@@ -11,14 +11,30 @@
 // LDS, and every thread (pixel p, position group g) accumulates its NPOS dot products from LDS with packed dot2
 // (fp16/bf16) or fma (fp32), fp32 accumulation.  D is exchanged through LDS for the 4-tap blend and written out
 // coalesced.  Tiles whose bounding box does not fit in LDS (incoherent flow) read f1 rows straight from L2/HBM.
+//
+// This file: the dispatch of roma_local_corr and three kernels,
+//   local_corr_kernel       any layout and dtype                      geometry and LDS layout: LCGeom<R>
+//   local_corr_nhwc_kernel  fp32 channels-last, LDS-DMA staging                                LCFast<R>
+//   local_corr_mfma_kernel  16-bit channels-last on the matrix cores, 8x4 / 4x4 tiles          LCM<R>
+// The steps they have in common are defined once, ahead of the kernels: block id -> tile (tile_of_block), a pixel's target
+// and clipped window (pixel_target, on lc::flow_target), the blend-and-store epilogue (blend_store), the ds_read_b128
+// lane groups (lane_group) and the count of DMA rounds (dma_rounds).  Each geometry struct states its kernel's LDS layout
+// once, as byte offsets and a total; the kernel carves the buffer up from the offsets and the launcher passes the total.
+// Written out twice on purpose: the per-pixel-patch path ("mode B") of the fp32 kernel (the MA = false instantiation of its
+// lambda) and of the MFMA kernel, the same algorithm with another swizzle, f0 row map and number of DMA rounds.  One
+// routine templated on the row map left the MFMA kernel within its registers but not local_corr_nhwc_kernel<float, R>:
+// r = 1 went from 68 to 80 VGPRs (7 -> 6 waves per SIMD), and the scratch of r = 2, 4, 7 from 32, 60, 152 to 44, 84, 160
+// bytes per lane (gfx950, hipcc -O3; profiles/local_corr_shared_code.txt).
 #include <type_traits>
 #include <cstdlib>
 #include "common.h"
 #include "lc_variants.h"
+#include "lc_device.h"
 
 namespace roma {
 namespace {
 
+// what a kernel reads (the kernel choice and the LDS sizes are the launchers' business)
 struct LCParams {
   const void* f0;
   const void* f1;
@@ -29,103 +45,187 @@ struct LCParams {
   int in_nhwc, out_nhwc;
   int tiles_x, tiles_y;
   int f1_shift;  // f1 batch item paired with f0's item b is (b + f1_shift) % B (forward_symmetric: B/2)
-  int variant;   // ROMA_LC_* kernel selection (16-bit channels-last, r <= 3)
-  int max_rows;  // LDS capacity in f1 rows (excluding the zero row)
   float scale;   // C^-1/2
 };
 
-template <int R> struct LCGeom;
-// TP pixels x PG position groups = 256 threads; NPOS = ceil((2R+2)^2 / PG) positions per thread
-template <> struct LCGeom<1> { static constexpr int TW = 8, TH = 8, PG = 4; };
-template <> struct LCGeom<2> { static constexpr int TW = 8, TH = 8, PG = 4; };
-template <> struct LCGeom<3> { static constexpr int TW = 8, TH = 8, PG = 4; };
-template <> struct LCGeom<4> { static constexpr int TW = 8, TH = 4, PG = 8; };
-template <> struct LCGeom<5> { static constexpr int TW = 8, TH = 4, PG = 8; };
-template <> struct LCGeom<6> { static constexpr int TW = 4, TH = 4, PG = 16; };
-template <> struct LCGeom<7> { static constexpr int TW = 4, TH = 4, PG = 16; };
-
 constexpr int kThreads = 256;
+
+// ------------------------------------------------------------------------------------------------------------------
+// Steps the three kernels of this file share.  Each is written once and inlined; the kernels keep what differs between
+// them: the reduction of the pixel windows to a box, the staging and the dot products.
+// ------------------------------------------------------------------------------------------------------------------
 
 // element address of (b, c, y, x) in a feature map
 __device__ __forceinline__ size_t feat_off(int nhwc, int b, int c, int y, int x, int pitch, int H, int W) {
   return nhwc ? (((size_t)b * H + y) * W + x) * pitch + c : (((size_t)b * pitch + c) * H + y) * W + x;
 }
 
-template <typename T, int R, int CC>
-__global__ __launch_bounds__(kThreads) void local_corr_kernel(LCParams p) {
-  using G = LCGeom<R>;
-  constexpr int TW = G::TW, TH = G::TH, TP = TW * TH, PG = G::PG;
-  constexpr int N1 = 2 * R + 1, N2 = 2 * R + 2, Q = N2 * N2, K = N1 * N1;
-  constexpr int NPOS = (Q + PG - 1) / PG;
-  constexpr int E16 = ElemTraits<T>::kPer16B;     // elements per 16-byte packet
-  constexpr int PK = CC / E16;                    // packets per LDS row
-  constexpr int ROW16 = PK + 1;                   // row stride in packets (+1 packet pad: odd stride -> no bank conflicts)
-  static_assert(TP * PG == kThreads, "geometry");
-  static_assert(CC % E16 == 0, "chunk");
-
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int* s_meta = reinterpret_cast<int*>(smem);                 // [0..3] bbox, [4] mode
-  int* s_x0 = s_meta + 8;
-  int* s_y0 = s_x0 + TP;
-  float* s_ax = reinterpret_cast<float*>(s_y0 + TP);
-  float* s_ay = s_ax + TP;
-  u32x4* s_f0 = reinterpret_cast<u32x4*>(s_ay + TP);          // TP rows
-  u32x4* s_f1 = s_f0 + TP * ROW16;                            // max_rows + 1 rows (last = zeros)
-  float* s_D = reinterpret_cast<float*>(s_f1);                // aliased after the channel loop: [TP][Q+1]
-
-  const int tid = threadIdx.x;
-  const int ntile = p.tiles_x * p.tiles_y;
+// block id -> batch item b and origin (ty0, tx0) of its TW x TH tile
+struct LCTile { int b, ty0, tx0; };
+template <int TW, int TH>
+__device__ __forceinline__ LCTile tile_of_block(int tiles_x, int tiles_y) {
+  const int ntile = tiles_x * tiles_y;
   const int wid = xcd_remap(blockIdx.x, gridDim.x);
   const int b = wid / ntile;
   const int t = wid - b * ntile;
-  const int ty0 = (t / p.tiles_x) * TH, tx0 = (t % p.tiles_x) * TW;
+  return {b, (t / tiles_x) * TH, (t % tiles_x) * TW};
+}
+
+// Target of image pixel (b, y, x): floor (x0, y0) and bilinear fraction (ax, ay) of the flow (identity grid without
+// one) in pixels, and its window [x0-R, x0+R+1] x [y0-R, y0+R+1] clipped to the map; `hit` is false when the window
+// misses the map (then lo > hi on some axis).
+struct LCTarget { int x0, y0; float ax, ay; int lox, loy, hix, hiy; bool hit; };
+template <int R>
+__device__ __forceinline__ LCTarget pixel_target(const float* flow, int b, int y, int x, int H, int W) {
+  LCTarget t;
+  float fx, fy;
+  if (flow) {
+    fx = flow[((size_t)(b * 2 + 0) * H + y) * W + x];
+    fy = flow[((size_t)(b * 2 + 1) * H + y) * W + x];
+  } else {
+    fx = -1.f + (2.f * x + 1.f) / W;
+    fy = -1.f + (2.f * y + 1.f) / H;
+  }
+  lc::flow_target(fx, fy, H, W, t.x0, t.y0, t.ax, t.ay);
+  t.lox = max(t.x0 - R, 0), t.hix = min(t.x0 + R + 1, W - 1);
+  t.loy = max(t.y0 - R, 0), t.hiy = min(t.y0 + R + 1, H - 1);
+  t.hit = t.lox <= t.hix && t.loy <= t.hiy;
+  return t;
+}
+
+// Epilogue: 4-tap blend of the integer-grid products s_D[pix][(2R+2)^2 (+1 pad)] with each pixel's fraction.  Output
+// element e of the tile's TP x (2R+1)^2 is (pixel, k) channels-last (consecutive threads = consecutive k of one pixel)
+// or (k, pixel) planar (consecutive pixels of one k).
+template <typename T, int R, int TP, int TW>
+__device__ __forceinline__ void blend_store_at(int e, T* out, int out_nhwc, int out_pitch, int b, int ty0, int tx0, int H, int W,
+                                               const float* s_D, const float* s_ax, const float* s_ay) {
+  constexpr int N1 = 2 * R + 1, N2 = 2 * R + 2, Q = N2 * N2, K = N1 * N1;
+  int pix, k;
+  if (out_nhwc) { pix = e / K; k = e - pix * K; } else { k = e / TP; pix = e - k * TP; }
+  const int y = ty0 + pix / TW, x = tx0 + pix % TW;
+  if (y >= H || x >= W) return;
+  const int iy = k / N1, ix = k - iy * N1;
+  const float ax = s_ax[pix], ay = s_ay[pix];
+  const float* d = s_D + pix * (Q + 1) + iy * N2 + ix;
+  const float top = d[0] + ax * (d[1] - d[0]);
+  const float bot = d[N2] + ax * (d[N2 + 1] - d[N2]);
+  out[feat_off(out_nhwc, b, k, y, x, out_pitch, H, W)] = from_f32<T>(top + ay * (bot - top));
+}
+// The whole epilogue of one thread.  local_corr_nhwc_kernel writes this loop out instead: with the loop inlined from here
+// its fp32 r = 4..7 instantiations, which sit at 128 VGPRs, spill 4 to 12 bytes more per lane (64/168/28/164 against 60/160/24/152
+// bytes of scratch), while the MFMA kernel at r = 6 takes 136 instead of 116 VGPRs with the loop written out
+// (profiles/local_corr_shared_code.txt).
+template <typename T, int R, int TP, int TW>
+__device__ __forceinline__ void blend_store(int tid, T* out, int out_nhwc, int out_pitch, int b, int ty0, int tx0, int H, int W,
+                                            const float* s_D, const float* s_ax, const float* s_ay) {
+  for (int e = tid; e < TP * (2 * R + 1) * (2 * R + 1); e += kThreads)
+    blend_store_at<T, R, TP, TW>(e, out, out_nhwc, out_pitch, b, ty0, tx0, H, W, s_D, s_ax, s_ay);
+}
+
+// ds_read_b128 serves a wavefront in four fixed 16-lane groups: lanes {0-3,12-15,20-27}, {4-11,16-19,28-31}, and the
+// same +32.  g16 = this thread's group among the workgroup's 16, idx = its place in the group.
+struct LaneGroup { int g16, idx; };
+__device__ __forceinline__ LaneGroup lane_group(int lane, int wave) {
+  const int l5 = lane & 31;
+  int hg, idx;
+  if (l5 < 4) { hg = 0; idx = l5; }
+  else if (l5 < 12) { hg = 1; idx = l5 - 4; }
+  else if (l5 < 16) { hg = 0; idx = l5 - 8; }
+  else if (l5 < 20) { hg = 1; idx = l5 - 8; }
+  else if (l5 < 28) { hg = 0; idx = l5 - 12; }
+  else { hg = 1; idx = l5 - 16; }
+  return {wave * 4 + (lane >> 5) * 2 + hg, idx};
+}
+
+// LDS-DMA rounds (one round = 256 threads x 16 bytes = 64 rows of 64 bytes) that cover `rows` staged rows, 16 at a time
+__host__ __device__ constexpr int dma_rounds(int rows) { return (((rows + 15) & ~15) * 4 + kThreads - 1) / kThreads; }
+
+constexpr int pow2_floor(int v) { return v >= 16 ? 16 : v >= 8 ? 8 : v >= 4 ? 4 : v >= 2 ? 2 : 1; }
+
+// LDS of the two LDS-DMA kernels (fp32 channels-last, 16-bit matrix cores), stated once for kernel and launcher: the
+// DMA'd rows (TP f0 rows + up to MAXR staged rows, in whole rounds), 16 all-zero rows (never a DMA target), the products
+// D[TP][Q+1], META words of boxes, then x0, y0, ax, ay per pixel.  Offsets in bytes.
+template <int TP, int MAXR, int Q, int META> struct LCStagedLds {
+  static constexpr int NL = dma_rounds(TP + MAXR);                  // DMA rounds of a full buffer
+  static constexpr int ZROW = NL * (kThreads / 4);                  // first zero row
+  static constexpr int ROWS_B = (NL * kThreads + 16 * 4) * 16, D_B = TP * (Q + 1) * 4, META_B = META * 4, PIX_B = TP * 4;
+  static constexpr int OFF_D = ROWS_B, OFF_META = OFF_D + D_B;
+  static constexpr int OFF_X0 = OFF_META + META_B, OFF_Y0 = OFF_X0 + PIX_B, OFF_AX = OFF_Y0 + PIX_B, OFF_AY = OFF_AX + PIX_B;
+  static constexpr int BYTES = ROWS_B + D_B + META_B + 4 * PIX_B;
+  static_assert(BYTES == OFF_AY + PIX_B, "LDS total != end of the last region");
+};
+
+// ------------------------------------------------------------------------------------------------------------------
+// Any layout and dtype.  TP pixels x PG position groups = 256 threads; NPOS = ceil((2R+2)^2 / PG) positions per thread.
+// LDS (bytes): 8 meta words, x0, y0, ax, ay per pixel, TP f0 rows, MAXROWS + 1 f1 rows (the last all zero); D[TP][Q+1]
+// aliases the f1 rows after the channel loop.  A row is one position's channel chunk plus a 16-byte pad (odd stride in
+// packets: no bank conflicts): 128 bytes of channels for small windows, 64 for r >= 4 (more rows fit).
+// ------------------------------------------------------------------------------------------------------------------
+template <int R> struct LCGeom {
+  static constexpr int TW = R <= 5 ? 8 : 4, TH = R <= 3 ? 8 : 4, TP = TW * TH, PG = kThreads / TP;
+  static constexpr int Q = (2 * R + 2) * (2 * R + 2);
+  static constexpr int CHUNK_B = R >= 4 ? 64 : 128, ROW_B = CHUNK_B + 16;
+  static constexpr int PIX_B = TP * 4;
+  static constexpr int OFF_X0 = 8 * 4, OFF_Y0 = OFF_X0 + PIX_B, OFF_AX = OFF_Y0 + PIX_B, OFF_AY = OFF_AX + PIX_B;
+  static constexpr int OFF_F0 = OFF_AY + PIX_B, OFF_F1 = OFF_F0 + TP * ROW_B;
+  // about 60 KiB per workgroup so that two workgroups share a CU
+  static constexpr int MAXROWS = (60 * 1024 - OFF_F1) / ROW_B - 1;  // capacity in f1 rows (excluding the zero row)
+  static constexpr int F1_B = (MAXROWS + 1) * ROW_B, D_B = TP * (Q + 1) * 4;
+  static constexpr int BYTES = 8 * 4 + 4 * PIX_B + TP * ROW_B + (F1_B > D_B ? F1_B : D_B);
+  static_assert(BYTES == OFF_F1 + (F1_B > D_B ? F1_B : D_B), "LDS total != end of the last region");
+};
+
+template <typename T, int R, int CC>
+__global__ __launch_bounds__(kThreads) void local_corr_kernel(LCParams p) {
+  using G = LCGeom<R>;
+  constexpr int TW = G::TW, TH = G::TH, TP = G::TP, PG = G::PG;
+  constexpr int N2 = 2 * R + 2, Q = G::Q;
+  constexpr int NPOS = (Q + PG - 1) / PG;
+  constexpr int E16 = ElemTraits<T>::kPer16B;     // elements per 16-byte packet
+  constexpr int PK = CC / E16;                    // packets per LDS row
+  constexpr int ROW16 = G::ROW_B / 16;            // row stride in packets
+  static_assert(CC * sizeof(T) == G::CHUNK_B && ROW16 == PK + 1, "chunk");
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int* s_meta = reinterpret_cast<int*>(smem);                 // [0..3] bbox
+  int* s_x0 = reinterpret_cast<int*>(smem + G::OFF_X0);
+  int* s_y0 = reinterpret_cast<int*>(smem + G::OFF_Y0);
+  float* s_ax = reinterpret_cast<float*>(smem + G::OFF_AX);
+  float* s_ay = reinterpret_cast<float*>(smem + G::OFF_AY);
+  u32x4* s_f0 = reinterpret_cast<u32x4*>(smem + G::OFF_F0);   // TP rows
+  u32x4* s_f1 = reinterpret_cast<u32x4*>(smem + G::OFF_F1);   // MAXROWS + 1 rows (last = zeros)
+  float* s_D = reinterpret_cast<float*>(s_f1);                // aliased after the channel loop: [TP][Q+1]
+
+  const int tid = threadIdx.x;
+  const LCTile tile = tile_of_block<TW, TH>(p.tiles_x, p.tiles_y);
+  const int b = tile.b, ty0 = tile.ty0, tx0 = tile.tx0;
   const int H = p.H, W = p.W;
 
   if (tid < 4) s_meta[tid] = (tid < 2) ? 0x7fffffff : -0x7fffffff;
   __syncthreads();
   if (tid < TP) {
     const int y = ty0 + tid / TW, x = tx0 + tid % TW;
-    int x0 = 0, y0 = 0;
-    float ax = 0.f, ay = 0.f;
-    const bool valid = (y < H) && (x < W);
-    if (valid) {
-      float fx, fy;
-      if (p.flow) {
-        fx = p.flow[((size_t)(b * 2 + 0) * H + y) * W + x];
-        fy = p.flow[((size_t)(b * 2 + 1) * H + y) * W + x];
-      } else {
-        fx = -1.f + (2.f * x + 1.f) / W;
-        fy = -1.f + (2.f * y + 1.f) / H;
-      }
-      float px = ((fx + 1.f) * W - 1.f) * 0.5f, py = ((fy + 1.f) * H - 1.f) * 0.5f;
-      // keep the integer conversion defined for wild / non-finite flow: such targets are fully outside the image
-      if (!(px > -1e6f && px < 1e6f)) px = -1e6f;
-      if (!(py > -1e6f && py < 1e6f)) py = -1e6f;
-      const float fx0 = floorf(px), fy0 = floorf(py);
-      ax = px - fx0;
-      ay = py - fy0;
-      x0 = (int)fx0;
-      y0 = (int)fy0;
-      const int lox = max(x0 - R, 0), hix = min(x0 + R + 1, W - 1);
-      const int loy = max(y0 - R, 0), hiy = min(y0 + R + 1, H - 1);
-      if (lox <= hix && loy <= hiy) {
-        atomicMin(&s_meta[0], lox);
-        atomicMin(&s_meta[1], loy);
-        atomicMax(&s_meta[2], hix);
-        atomicMax(&s_meta[3], hiy);
+    LCTarget t{};
+    if (y < H && x < W) {
+      t = pixel_target<R>(p.flow, b, y, x, H, W);
+      if (t.hit) {
+        atomicMin(&s_meta[0], t.lox);
+        atomicMin(&s_meta[1], t.loy);
+        atomicMax(&s_meta[2], t.hix);
+        atomicMax(&s_meta[3], t.hiy);
       }
     }
-    s_x0[tid] = x0;
-    s_y0[tid] = y0;
-    s_ax[tid] = ax;
-    s_ay[tid] = ay;
+    s_x0[tid] = t.x0;
+    s_y0[tid] = t.y0;
+    s_ax[tid] = t.ax;
+    s_ay[tid] = t.ay;
   }
   __syncthreads();
   const int bx0 = s_meta[0], by0 = s_meta[1];
   const bool empty = s_meta[2] < bx0 || s_meta[3] < by0;       // every window of the tile is outside the image
   const int bw = empty ? 0 : s_meta[2] - bx0 + 1, bh = empty ? 0 : s_meta[3] - by0 + 1;
   const int nrows = bw * bh;
-  const bool staged = nrows <= p.max_rows;                     // else: read f1 rows from global memory directly
+  const bool staged = nrows <= G::MAXROWS;                   // else: read f1 rows from global memory directly
   const int zero_row = staged ? nrows : 0;
 
   // per-thread work list: pixel pp, positions q = g*NPOS .. g*NPOS+NPOS-1
@@ -241,20 +341,7 @@ __global__ __launch_bounds__(kThreads) void local_corr_kernel(LCParams p) {
     if (q < Q) s_D[pp * (Q + 1) + q] = acc[i] * p.scale;
   }
   __syncthreads();
-  T* out = static_cast<T*>(p.out);
-  for (int e = tid; e < TP * K; e += kThreads) {
-    int pix, k;
-    if (p.out_nhwc) { pix = e / K; k = e - pix * K; } else { k = e / TP; pix = e - k * TP; }
-    const int y = ty0 + pix / TW, x = tx0 + pix % TW;
-    if (y >= H || x >= W) continue;
-    const int iy = k / N1, ix = k - iy * N1;
-    const float ax = s_ax[pix], ay = s_ay[pix];
-    const float* d = s_D + pix * (Q + 1) + iy * N2 + ix;
-    const float top = d[0] + ax * (d[1] - d[0]);
-    const float bot = d[N2] + ax * (d[N2 + 1] - d[N2]);
-    const float v = top + ay * (bot - top);
-    out[feat_off(p.out_nhwc, b, k, y, x, p.out_pitch, H, W)] = from_f32<T>(v);
-  }
+  blend_store<T, R, TP, TW>(tid, static_cast<T*>(p.out), p.out_nhwc, p.out_pitch, b, ty0, tx0, H, W, s_D, s_ax, s_ay);
 }
 
 
@@ -276,6 +363,7 @@ template <int R> struct LCFast {
   static constexpr int TP = R <= 5 ? 32 : 16;                       // pixels per tile
   static constexpr int TW = R <= 5 ? 8 : 4, TH = TP / TW;
   static constexpr int MAXR = R <= 3 ? 384 : (R <= 5 ? 512 : 640);  // LDS capacity in staged rows (multiple of 16)
+  using Lds = LCStagedLds<TP, MAXR, (2 * R + 2) * (2 * R + 2), 8>;  // meta: [0..3] tile box
 };
 
 __device__ __forceinline__ int swz(int row, int k) { return row * 4 + (k ^ ((row >> 2) & 3)); }
@@ -289,13 +377,12 @@ __device__ __forceinline__ void dma16(const void* gsrc, unsigned char* lds_wave_
 #endif
 }
 
-constexpr int pow2_floor(int v) { return v >= 16 ? 16 : v >= 8 ? 8 : v >= 4 ? 4 : v >= 2 ? 2 : 1; }
-
 template <typename T, int R>
 __global__ __launch_bounds__(kThreads, 4) void local_corr_nhwc_kernel(LCParams p) {   // <= 128 VGPRs: 4 workgroups / CU
   using G = LCFast<R>;
+  using L = typename G::Lds;
   constexpr int TW = G::TW, TH = G::TH, TP = G::TP;
-  constexpr int N1 = 2 * R + 1, N2 = 2 * R + 2, Q = N2 * N2, K = N1 * N1;
+  constexpr int N2 = 2 * R + 2, Q = N2 * N2;
   constexpr int NPIX = TP / 16;                 // pixels handled (one after the other) by each 16-lane group
   constexpr int NIT = (Q + 15) / 16;            // window positions per lane and pixel
   constexpr int QP = NIT * 16;                  // rows of one per-pixel patch (mode B)
@@ -303,25 +390,20 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_nhwc_kernel(LCParams p
   constexpr int PK = 4, CC = PK * E16;
   constexpr int MAXR = G::MAXR;
   constexpr int SB = pow2_floor(MAXR / QP);     // pixels whose private patches fit in LDS together (mode B)
-  constexpr int NROWS = TP + MAXR;              // f0 rows + staged rows
-  constexpr int NL = (NROWS * PK + kThreads - 1) / kThreads;   // DMA rounds (64 rows each)
-  constexpr int ZROW = NL * (kThreads / PK);    // 16 all-zero rows right after the DMA'd buffer (never a DMA target)
+  constexpr int NL = L::NL, ZROW = L::ZROW;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32x4* s_rows = reinterpret_cast<u32x4*>(smem);             // row r, packet k at s_rows[swz(r, k)]
-  float* s_D = reinterpret_cast<float*>(s_rows + NL * kThreads + 16 * PK);   // [TP][Q+1] integer-grid dot products
-  int* s_meta = reinterpret_cast<int*>(s_D + TP * (Q + 1));
-  int* s_x0 = s_meta + 8;
-  int* s_y0 = s_x0 + TP;
-  float* s_ax = reinterpret_cast<float*>(s_y0 + TP);
-  float* s_ay = s_ax + TP;
+  float* s_D = reinterpret_cast<float*>(smem + L::OFF_D);     // [TP][Q+1] integer-grid dot products
+  int* s_meta = reinterpret_cast<int*>(smem + L::OFF_META);
+  int* s_x0 = reinterpret_cast<int*>(smem + L::OFF_X0);
+  int* s_y0 = reinterpret_cast<int*>(smem + L::OFF_Y0);
+  float* s_ax = reinterpret_cast<float*>(smem + L::OFF_AX);
+  float* s_ay = reinterpret_cast<float*>(smem + L::OFF_AY);
 
   const int tid = threadIdx.x;
-  const int ntile = p.tiles_x * p.tiles_y;
-  const int wid = xcd_remap(blockIdx.x, gridDim.x);
-  const int b = wid / ntile;
-  const int t = wid - b * ntile;
-  const int ty0 = (t / p.tiles_x) * TH, tx0 = (t % p.tiles_x) * TW;
+  const LCTile tile = tile_of_block<TW, TH>(p.tiles_x, p.tiles_y);
+  const int b = tile.b, ty0 = tile.ty0, tx0 = tile.tx0;
   const int H = p.H, W = p.W;
 
   if (tid < 4) s_meta[tid] = (tid < 2) ? 0x7fffffff : -0x7fffffff;
@@ -329,38 +411,20 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_nhwc_kernel(LCParams p
   __syncthreads();
   if (tid < TP) {
     const int y = ty0 + tid / TW, x = tx0 + tid % TW;
-    int x0 = 0, y0 = 0;
-    float ax = 0.f, ay = 0.f;
+    LCTarget t{};
     if (y < H && x < W) {
-      float fx, fy;
-      if (p.flow) {
-        fx = p.flow[((size_t)(b * 2 + 0) * H + y) * W + x];
-        fy = p.flow[((size_t)(b * 2 + 1) * H + y) * W + x];
-      } else {
-        fx = -1.f + (2.f * x + 1.f) / W;
-        fy = -1.f + (2.f * y + 1.f) / H;
-      }
-      float px = ((fx + 1.f) * W - 1.f) * 0.5f, py = ((fy + 1.f) * H - 1.f) * 0.5f;
-      if (!(px > -1e6f && px < 1e6f)) px = -1e6f;
-      if (!(py > -1e6f && py < 1e6f)) py = -1e6f;
-      const float fx0 = floorf(px), fy0 = floorf(py);
-      ax = px - fx0;
-      ay = py - fy0;
-      x0 = (int)fx0;
-      y0 = (int)fy0;
-      const int lox = max(x0 - R, 0), hix = min(x0 + R + 1, W - 1);
-      const int loy = max(y0 - R, 0), hiy = min(y0 + R + 1, H - 1);
-      if (lox <= hix && loy <= hiy) {
-        atomicMin(&s_meta[0], lox);
-        atomicMin(&s_meta[1], loy);
-        atomicMax(&s_meta[2], hix);
-        atomicMax(&s_meta[3], hiy);
+      t = pixel_target<R>(p.flow, b, y, x, H, W);
+      if (t.hit) {
+        atomicMin(&s_meta[0], t.lox);
+        atomicMin(&s_meta[1], t.loy);
+        atomicMax(&s_meta[2], t.hix);
+        atomicMax(&s_meta[3], t.hiy);
       }
     }
-    s_x0[tid] = x0;
-    s_y0[tid] = y0;
-    s_ax[tid] = ax;
-    s_ay[tid] = ay;
+    s_x0[tid] = t.x0;
+    s_y0[tid] = t.y0;
+    s_ax[tid] = t.ax;
+    s_ay[tid] = t.ay;
   }
   __syncthreads();
   const int bx0 = s_meta[0], by0 = s_meta[1];
@@ -372,19 +436,8 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_nhwc_kernel(LCParams p
   // SB pixels at a time get a private (2r+2)^2 patch each (16-row aligned), several passes.
   const bool modeA = bwp * bh <= MAXR;
 
-  // 16-lane ds_read_b128 service groups of a wavefront: {0-3,12-15,20-27}, {4-11,16-19,28-31}, and the same +32
-  int g16, idx;
-  {
-    const int lane = tid & 63, l5 = lane & 31;
-    int hg;
-    if (l5 < 4) { hg = 0; idx = l5; }
-    else if (l5 < 12) { hg = 1; idx = l5 - 4; }
-    else if (l5 < 16) { hg = 0; idx = l5 - 8; }
-    else if (l5 < 20) { hg = 1; idx = l5 - 8; }
-    else if (l5 < 28) { hg = 0; idx = l5 - 12; }
-    else { hg = 1; idx = l5 - 16; }
-    g16 = (tid >> 6) * 4 + (lane >> 5) * 2 + hg;
-  }
+  const LaneGroup lg = lane_group(tid & 63, tid >> 6);
+  const int g16 = lg.g16, idx = lg.idx;
   const T* f0 = static_cast<const T*>(p.f0) + (size_t)b * H * W * p.f0_pitch;
   const T* f1 = static_cast<const T*>(p.f1) + (size_t)((b + p.f1_shift) % p.B) * H * W * p.f1_pitch;
 
@@ -461,7 +514,7 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_nhwc_kernel(LCParams p
         }
         src[l] = base + ((size_t)y * W + x) * pitch + k * E16;
       }
-      const int nl_used = (((used_rows + 15) & ~15) * PK + kThreads - 1) / kThreads;   // DMA rounds that carry data
+      const int nl_used = dma_rounds(used_rows);                // DMA rounds that carry data
       for (int c0 = 0; c0 < p.C; c0 += CC) {
 #pragma unroll
         for (int l = 0; l < NL; ++l)
@@ -492,34 +545,17 @@ __global__ __launch_bounds__(kThreads, 4) void local_corr_nhwc_kernel(LCParams p
   if (modeA) run(std::true_type{}); else run(std::false_type{});
   __syncthreads();
   T* out = static_cast<T*>(p.out);
-  for (int e = tid; e < TP * K; e += kThreads) {
-    int pix, k;
-    if (p.out_nhwc) { pix = e / K; k = e - pix * K; } else { k = e / TP; pix = e - k * TP; }
-    const int y = ty0 + pix / TW, x = tx0 + pix % TW;
-    if (y >= H || x >= W) continue;
-    const int iy = k / N1, ix = k - iy * N1;
-    const float ax = s_ax[pix], ay = s_ay[pix];
-    const float* d = s_D + pix * (Q + 1) + iy * N2 + ix;
-    const float top = d[0] + ax * (d[1] - d[0]);
-    const float bot = d[N2] + ax * (d[N2 + 1] - d[N2]);
-    out[feat_off(p.out_nhwc, b, k, y, x, p.out_pitch, H, W)] = from_f32<T>(top + ay * (bot - top));
-  }
+  for (int e = tid; e < TP * (2 * R + 1) * (2 * R + 1); e += kThreads)     // blend_store's loop, written out: see its comment
+    blend_store_at<T, R, TP, TW>(e, out, p.out_nhwc, p.out_pitch, b, ty0, tx0, H, W, s_D, s_ax, s_ay);
 }
 
 template <typename T, int R>
 int launch_lc_nhwc(LCParams p, hipStream_t stream) {
   using G = LCFast<R>;
-  constexpr int TP = G::TP, Q = (2 * R + 2) * (2 * R + 2);
-  constexpr int NROWS = TP + G::MAXR;
-  constexpr int NL = (NROWS * 4 + kThreads - 1) / kThreads;
   p.tiles_x = (p.W + G::TW - 1) / G::TW;
   p.tiles_y = (p.H + G::TH - 1) / G::TH;
-  p.max_rows = G::MAXR;
-  const size_t smem = (size_t)NL * kThreads * 16 + 16 * 4 * 16      // DMA'd rows + 16 zero rows
-                      + (size_t)TP * (Q + 1) * 4                     // D exchange
-                      + (8 + 2 * TP) * 4 + 2 * TP * 4;              // meta
   const int grid = p.B * p.tiles_x * p.tiles_y;
-  hipLaunchKernelGGL((local_corr_nhwc_kernel<T, R>), dim3(grid), dim3(kThreads), smem, stream, p);
+  hipLaunchKernelGGL((local_corr_nhwc_kernel<T, R>), dim3(grid), dim3(kThreads), G::Lds::BYTES, stream, p);
   ROMA_CHECK_LAUNCH();
 }
 
@@ -546,48 +582,33 @@ template <int R> struct LCM {
   static constexpr int GHMAX = N2 + 10;                      // union rows a group may span
   static constexpr int NB = (GHMAX * NRUN + WPG - 1) / WPG;  // accumulator blocks per wavefront
   static constexpr int MAXR = R <= 3 ? 384 : 704;            // staged rows
+  using Lds = LCStagedLds<TP, MAXR, N2 * N2, 8 + 4 * NG>;    // meta: [0..3] tile box, [8+4g ..] group boxes
 };
-
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 b8_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float4_t mfma16(const u32x4& a, const u32x4& b, float4_t c, half_t) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ float4_t mfma16(const u32x4& a, const u32x4& b, float4_t c, bf16_t) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8_t, a), __builtin_bit_cast(b8_t, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int swz1(int row, int k) { return row * 4 + (k ^ ((row >> 2) & 1)); }
 
 template <typename T, int R>
 __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p) {
   using M = LCM<R>;
   constexpr int NG = M::NG, TP = M::TP, TW = M::TW, TH = M::TH, WPG = M::WPG, NRUN = M::NRUN, WC = M::WC;
   constexpr int GHMAX = M::GHMAX, NB = M::NB, MAXR = M::MAXR;
-  constexpr int N1 = 2 * R + 1, N2 = 2 * R + 2, Q = N2 * N2, K = N1 * N1;
+  constexpr int N2 = 2 * R + 2, Q = N2 * N2;
   constexpr int NIT = (Q + 15) / 16, QP = NIT * 16;
   constexpr int E16 = 8, PK = 4, CC = PK * E16;
   constexpr int SB = pow2_floor(MAXR / QP);
-  constexpr int NL = ((TP + MAXR) * PK + kThreads - 1) / kThreads;
-  constexpr int ZROW = NL * (kThreads / PK);
-  constexpr int BODY16 = NL * kThreads + 16 * PK;          // staged rows + 16 zero rows
+  using L = typename M::Lds;
+  constexpr int NL = L::NL, ZROW = L::ZROW;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* s_rows = reinterpret_cast<u32x4*>(smem);             // staged rows
-  float* s_D = reinterpret_cast<float*>(s_rows + BODY16);     // [TP][Q+1], mode B only
-  int* s_meta = reinterpret_cast<int*>(s_D + TP * (Q + 1));   // [0..3] tile box, [8+4g ..] group boxes
-  int* s_x0 = s_meta + 8 + 4 * NG;
-  int* s_y0 = s_x0 + TP;
-  float* s_ax = reinterpret_cast<float*>(s_y0 + TP);
-  float* s_ay = s_ax + TP;
+  u32x4* s_rows = reinterpret_cast<u32x4*>(smem);             // staged rows, packet k of row r at s_rows[lc::swzr(r, k)]
+  float* s_D = reinterpret_cast<float*>(smem + L::OFF_D);     // [TP][Q+1] per-pixel window images
+  int* s_meta = reinterpret_cast<int*>(smem + L::OFF_META);   // [0..3] tile box, [8+4g ..] group boxes
+  int* s_x0 = reinterpret_cast<int*>(smem + L::OFF_X0);
+  int* s_y0 = reinterpret_cast<int*>(smem + L::OFF_Y0);
+  float* s_ax = reinterpret_cast<float*>(smem + L::OFF_AX);
+  float* s_ay = reinterpret_cast<float*>(smem + L::OFF_AY);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int ntile = p.tiles_x * p.tiles_y;
-  const int wid = xcd_remap(blockIdx.x, gridDim.x);
-  const int b = wid / ntile;
-  const int t = wid - b * ntile;
-  const int ty0 = (t / p.tiles_x) * TH, tx0 = (t % p.tiles_x) * TW;
+  const LCTile tile = tile_of_block<TW, TH>(p.tiles_x, p.tiles_y);
+  const int b = tile.b, ty0 = tile.ty0, tx0 = tile.tx0;
   const int H = p.H, W = p.W;
 
   for (int i = tid; i < 16 * PK; i += kThreads) s_rows[ZROW * PK + i] = u32x4{0, 0, 0, 0};
@@ -597,35 +618,17 @@ __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p
   // kernel in the ablation of DESIGN.md §3.1) ----
   if (wave == 0) {
     const int y = ty0 + tid / TW, x = tx0 + tid % TW;
-    int x0 = 0, y0 = 0;
-    float ax = 0.f, ay = 0.f;
+    LCTarget t{};
     int lox = 0x3fffffff, loy = 0x3fffffff, hix = -0x3fffffff, hiy = -0x3fffffff;
     if (tid < TP && y < H && x < W) {
-      float fx, fy;
-      if (p.flow) {
-        fx = p.flow[((size_t)(b * 2 + 0) * H + y) * W + x];
-        fy = p.flow[((size_t)(b * 2 + 1) * H + y) * W + x];
-      } else {
-        fx = -1.f + (2.f * x + 1.f) / W;
-        fy = -1.f + (2.f * y + 1.f) / H;
-      }
-      float px = ((fx + 1.f) * W - 1.f) * 0.5f, py = ((fy + 1.f) * H - 1.f) * 0.5f;
-      if (!(px > -1e6f && px < 1e6f)) px = -1e6f;
-      if (!(py > -1e6f && py < 1e6f)) py = -1e6f;
-      const float fx0 = floorf(px), fy0 = floorf(py);
-      ax = px - fx0;
-      ay = py - fy0;
-      x0 = (int)fx0;
-      y0 = (int)fy0;
-      const int a0 = max(x0 - R, 0), a1 = min(x0 + R + 1, W - 1);
-      const int b0 = max(y0 - R, 0), b1 = min(y0 + R + 1, H - 1);
-      if (a0 <= a1 && b0 <= b1) { lox = a0; hix = a1; loy = b0; hiy = b1; }
+      t = pixel_target<R>(p.flow, b, y, x, H, W);
+      if (t.hit) { lox = t.lox; hix = t.hix; loy = t.loy; hiy = t.hiy; }
     }
     if (tid < TP) {
-      s_x0[tid] = x0;
-      s_y0[tid] = y0;
-      s_ax[tid] = ax;
-      s_ay[tid] = ay;
+      s_x0[tid] = t.x0;
+      s_y0[tid] = t.y0;
+      s_ax[tid] = t.ax;
+      s_ay[tid] = t.ay;
     }
     // pixel tid = (ty, tx) = (tid / TW, tid % TW); its 4x4 group is tx >> 2.  Reduce over every lane bit except the
     // group bit(s) first (group boxes), then over those (tile box).  Lanes >= TP carry neutral values.
@@ -671,7 +674,7 @@ __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p
     const float inv_bw = 1.0f / (float)bw;
     const T* src[NL];
     const int used_rows = TP + bw * bh;
-    const int nl_used = (((used_rows + 15) & ~15) * PK + kThreads - 1) / kThreads;
+    const int nl_used = dma_rounds(used_rows);
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
       if (l >= nl_used) { src[l] = f0; continue; }            // never issued
@@ -707,9 +710,9 @@ __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p
       const int blk = sub + WPG * j;
       const int ry = blk / NRUN, run = blk - ry * NRUN;
       const int row = (blk < gh * NRUN ? TP + (gy0 - by0 + ry) * bw + (gx0 - bx0 + 16 * run) : ZROW) + n;
-      bidx[j] = swz1(row, ks);
+      bidx[j] = lc::swzr(row, ks);
     }
-    const int aidx = swz1(gi * 16 + n, ks);
+    const int aidx = lc::swzr(gi * 16 + n, ks);
     float4_t acc[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) acc[j] = float4_t{0.f, 0.f, 0.f, 0.f};
@@ -720,7 +723,7 @@ __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p
       __syncthreads();
       const u32x4 a = s_rows[aidx];
 #pragma unroll
-      for (int j = 0; j < NB; ++j) acc[j] = mfma16(a, s_rows[bidx[j]], acc[j], T{});
+      for (int j = 0; j < NB; ++j) acc[j] = lc::mfma16r(a, s_rows[bidx[j]], acc[j], T{});
       __syncthreads();
     }
     // accumulators -> the per-pixel window images s_D[pix][dy*N2+dx] directly: lane (n, kg) of block (ry, run) holds the
@@ -750,34 +753,13 @@ __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p
       }
     }
     __syncthreads();
-    for (int e = tid; e < TP * K; e += kThreads) {
-      int pix, k;
-      if (p.out_nhwc) { pix = e / K; k = e - pix * K; } else { k = e / TP; pix = e - k * TP; }
-      const int y = ty0 + pix / TW, x = tx0 + pix % TW;
-      if (y >= H || x >= W) continue;
-      const int iy = k / N1, ix = k - iy * N1;
-      const float ax = s_ax[pix], ay = s_ay[pix];
-      const float* d = s_D + pix * (Q + 1) + iy * N2 + ix;
-      const float top = d[0] + ax * (d[1] - d[0]);
-      const float bot = d[N2] + ax * (d[N2 + 1] - d[N2]);
-      out[feat_off(p.out_nhwc, b, k, y, x, p.out_pitch, H, W)] = from_f32<T>(top + ay * (bot - top));
-    }
+    blend_store<T, R, TP, TW>(tid, out, p.out_nhwc, p.out_pitch, b, ty0, tx0, H, W, s_D, s_ax, s_ay);
     return;
   }
 
   // =========================== incoherent tile: per-pixel patches on the VALU (mode B) ===========================
-  int g16, idx;
-  {
-    const int l5 = lane & 31;
-    int hg;
-    if (l5 < 4) { hg = 0; idx = l5; }
-    else if (l5 < 12) { hg = 1; idx = l5 - 4; }
-    else if (l5 < 16) { hg = 0; idx = l5 - 8; }
-    else if (l5 < 20) { hg = 1; idx = l5 - 8; }
-    else if (l5 < 28) { hg = 0; idx = l5 - 12; }
-    else { hg = 1; idx = l5 - 16; }
-    g16 = wave * 4 + (lane >> 5) * 2 + hg;
-  }
+  const LaneGroup lg = lane_group(lane, wave);
+  const int g16 = lg.g16, idx = lg.idx;
   constexpr int UB = (SB * NIT + 15) / 16;
   for (int pass = 0; pass < (TP + SB - 1) / SB; ++pass) {
     int pixw[UB], qw[UB], rowidx[UB];
@@ -824,7 +806,7 @@ __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p
       }
       src[l] = base + ((size_t)y * W + x) * pitch + k * E16;
     }
-    const int nl_used = (((used_rows + 15) & ~15) * PK + kThreads - 1) / kThreads;
+    const int nl_used = dma_rounds(used_rows);
     for (int c0 = 0; c0 < p.C; c0 += CC) {
 #pragma unroll
       for (int l = 0; l < NL; ++l)
@@ -836,7 +818,7 @@ __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p
         const int r0 = rowidx[w];
         float sacc = acc[w];
 #pragma unroll
-        for (int k = 0; k < PK; ++k) sacc = dot16<T>(s_rows[swz1(prow, k)], s_rows[swz1(r0, k)], sacc);
+        for (int k = 0; k < PK; ++k) sacc = dot16<T>(s_rows[lc::swzr(prow, k)], s_rows[lc::swzr(r0, k)], sacc);
         acc[w] = sacc;
       }
       __syncthreads();
@@ -846,32 +828,17 @@ __global__ __launch_bounds__(kThreads, 2) void local_corr_mfma_kernel(LCParams p
       if (qw[w] < Q && pixw[w] >= 0) s_D[pixw[w] * (Q + 1) + qw[w]] = acc[w] * p.scale;
   }
   __syncthreads();
-  for (int e = tid; e < TP * K; e += kThreads) {
-    int pix, k;
-    if (p.out_nhwc) { pix = e / K; k = e - pix * K; } else { k = e / TP; pix = e - k * TP; }
-    const int y = ty0 + pix / TW, x = tx0 + pix % TW;
-    if (y >= H || x >= W) continue;
-    const int iy = k / N1, ix = k - iy * N1;
-    const float ax = s_ax[pix], ay = s_ay[pix];
-    const float* d = s_D + pix * (Q + 1) + iy * N2 + ix;
-    const float top = d[0] + ax * (d[1] - d[0]);
-    const float bot = d[N2] + ax * (d[N2 + 1] - d[N2]);
-    out[feat_off(p.out_nhwc, b, k, y, x, p.out_pitch, H, W)] = from_f32<T>(top + ay * (bot - top));
-  }
+  blend_store<T, R, TP, TW>(tid, out, p.out_nhwc, p.out_pitch, b, ty0, tx0, H, W, s_D, s_ax, s_ay);
 }
 
 template <typename T, int R>
 int launch_lc_mfma(LCParams p, hipStream_t stream) {
   using M = LCM<R>;
-  constexpr int Q = (2 * R + 2) * (2 * R + 2);
-  constexpr int NL = ((M::TP + M::MAXR) * 4 + kThreads - 1) / kThreads;
-  constexpr int BODY16 = NL * kThreads + 64;
   p.tiles_x = (p.W + M::TW - 1) / M::TW;
   p.tiles_y = (p.H + M::TH - 1) / M::TH;
-  p.max_rows = M::MAXR;
-  const size_t smem = (size_t)BODY16 * 16 + (size_t)M::TP * (Q + 1) * 4 + (8 + 4 * M::NG + 2 * M::TP) * 4 + 2 * M::TP * 4;
+  constexpr int smem = M::Lds::BYTES;
   static std::atomic<uint64_t> attr_done{0};
-  if (int rc = ensure_dyn_smem(reinterpret_cast<const void*>(local_corr_mfma_kernel<T, R>), (int)smem, attr_done, "roma_local_corr")) return rc;
+  if (int rc = ensure_dyn_smem(reinterpret_cast<const void*>(local_corr_mfma_kernel<T, R>), smem, attr_done, "roma_local_corr")) return rc;
   const int grid = p.B * p.tiles_x * p.tiles_y;
   hipLaunchKernelGGL((local_corr_mfma_kernel<T, R>), dim3(grid), dim3(kThreads), smem, stream, p);
   ROMA_CHECK_LAUNCH();
@@ -880,26 +847,16 @@ int launch_lc_mfma(LCParams p, hipStream_t stream) {
 template <typename T, int R>
 int launch_lc(LCParams p, hipStream_t stream) {
   using G = LCGeom<R>;
-  // LDS row = one position's channel chunk: 128 bytes for small windows, 64 bytes for r >= 4 (more rows fit)
-  constexpr int CC = (R >= 4 ? 64 : 128) / (int)sizeof(T);
-  constexpr int TP = G::TW * G::TH, Q = (2 * R + 2) * (2 * R + 2);
-  constexpr int ROWB = (CC / ElemTraits<T>::kPer16B + 1) * 16;
+  constexpr int CC = G::CHUNK_B / (int)sizeof(T);               // channels per LDS row
   p.tiles_x = (p.W + G::TW - 1) / G::TW;
   p.tiles_y = (p.H + G::TH - 1) / G::TH;
-  // LDS budget: about 60 KiB per workgroup so that two workgroups share a CU
-  const int meta = (8 + 2 * TP) * 4 + 2 * TP * 4;
-  const int budget = 60 * 1024;
-  p.max_rows = (budget - meta - TP * ROWB) / ROWB - 1;
-  const int need_D = TP * (Q + 1) * 4;
-  size_t smem = (size_t)meta + (size_t)TP * ROWB + (size_t)(p.max_rows + 1) * ROWB;
-  if (smem < (size_t)meta + (size_t)TP * ROWB + need_D) smem = (size_t)meta + (size_t)TP * ROWB + need_D;
   const int grid = p.B * p.tiles_x * p.tiles_y;
-  hipLaunchKernelGGL((local_corr_kernel<T, R, CC>), dim3(grid), dim3(kThreads), smem, stream, p);
+  hipLaunchKernelGGL((local_corr_kernel<T, R, CC>), dim3(grid), dim3(kThreads), G::BYTES, stream, p);
   ROMA_CHECK_LAUNCH();
 }
 
 template <typename T, int R>
-int launch_any(const LCParams& p, hipStream_t s) {
+int launch_any(const LCParams& p, int variant, hipStream_t s) {
   constexpr int CC = 4 * ElemTraits<T>::kPer16B;                // the fast paths stream whole 64-byte channel chunks
   if (!(p.in_nhwc && p.C % CC == 0)) return launch_lc<T, R>(p, s);
   if constexpr (sizeof(T) == 2) {
@@ -915,7 +872,7 @@ int launch_any(const LCParams& p, hipStream_t s) {
     const bool t8_ok = R <= 3 && p.C % 32 == 0 && (size_t)p.H * p.W * (size_t)(p.f0_pitch > p.f1_pitch ? p.f0_pitch : p.f1_pitch) * 2 < (1ull << 32);
     const bool rows_ok = local_corr_rows_supports(p.C, R, p.H, p.W) && nt8 < (1 << 21) &&
                          (size_t)p.H * p.W * (size_t)(p.f0_pitch > p.f1_pitch ? p.f0_pitch : p.f1_pitch) * 2 < (1ull << 32);
-    int v = p.variant;
+    int v = variant;
     if (v == ROMA_LC_AUTO) v = rows_ok ? ROMA_LC_ROWS8 : (t8_ok && nt8 >= 2048) ? ROMA_LC_TILE8X8 : ROMA_LC_TILE8X4;
     if (v == ROMA_LC_ROWS8 && !rows_ok) v = ROMA_LC_TILE8X8;
     if (v == ROMA_LC_TILE8X8 && !t8_ok) v = ROMA_LC_TILE8X4;
@@ -936,15 +893,15 @@ int launch_any(const LCParams& p, hipStream_t s) {
 }
 
 template <typename T>
-int dispatch_r(const LCParams& p, int r, hipStream_t s) {
+int dispatch_r(const LCParams& p, int r, int variant, hipStream_t s) {
   switch (r) {
-    case 1: return launch_any<T, 1>(p, s);
-    case 2: return launch_any<T, 2>(p, s);
-    case 3: return launch_any<T, 3>(p, s);
-    case 4: return launch_any<T, 4>(p, s);
-    case 5: return launch_any<T, 5>(p, s);
-    case 6: return launch_any<T, 6>(p, s);
-    case 7: return launch_any<T, 7>(p, s);
+    case 1: return launch_any<T, 1>(p, variant, s);
+    case 2: return launch_any<T, 2>(p, variant, s);
+    case 3: return launch_any<T, 3>(p, variant, s);
+    case 4: return launch_any<T, 4>(p, variant, s);
+    case 5: return launch_any<T, 5>(p, variant, s);
+    case 6: return launch_any<T, 6>(p, variant, s);
+    case 7: return launch_any<T, 7>(p, variant, s);
   }
   set_error("roma_local_corr: radius %d outside 1..7", r);
   return ROMA_E_UNSUPPORTED;
@@ -980,12 +937,11 @@ extern "C" int roma_local_corr(const void* f0, const void* f1, const float* flow
   p.in_nhwc = layout == ROMA_NHWC; p.out_nhwc = out_layout == ROMA_NHWC;
   p.scale = 1.0f / sqrtf((float)C);
   p.f1_shift = f1_batch_shift;
-  p.variant = variant;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (dtype) {
-    case ROMA_F32: return dispatch_r<float>(p, r, s);
-    case ROMA_F16: return dispatch_r<half_t>(p, r, s);
-    case ROMA_BF16: return dispatch_r<bf16_t>(p, r, s);
+    case ROMA_F32: return dispatch_r<float>(p, r, variant, s);
+    case ROMA_F16: return dispatch_r<half_t>(p, r, variant, s);
+    case ROMA_BF16: return dispatch_r<bf16_t>(p, r, variant, s);
   }
   set_error("roma_local_corr: unknown dtype %d", dtype);
   return ROMA_E_DTYPE;

@@ -87,6 +87,39 @@ def test_local_corr_full_sizes_vs_oracle(shape):
     assert maxerr(out, ref) < 5e-5
 
 
+_ORACLE_LC_RADII = {}
+
+
+def _oracle_lc_radius(r):
+    """fp32 inputs of shape (1, 32, 30, 34) with coherent flow and a pasted block of adversarial targets, and the oracle's result,
+    computed once per radius.  No NaN / out-of-range entries: the oracle does not define them."""
+    if r not in _ORACLE_LC_RADII:
+        B, C, h, w = 1, 32, 30, 34
+        f0 = H.T(R.normal(f"lcrad.{r}.f0", (B, C, h, w)))
+        f1 = H.T(R.normal(f"lcrad.{r}.f1", (B, C, h, w)))
+        flow = R.coherent_flow(f"lcrad.{r}.flow", B, h, w)
+        adv = R.adversarial_flow(f"lcrad.{r}.adv", B, h, w)
+        flow[:, :, h // 3: 2 * h // 3, w // 4: w // 2] = adv[:, :, h // 3: 2 * h // 3, w // 4: w // 2]
+        flow = H.T(flow)
+        _ORACLE_LC_RADII[r] = (f0, f1, flow, _O().local_correlation(f0, f1, r, flow=flow))
+    return _ORACLE_LC_RADII[r]
+
+
+@pytest.mark.parametrize("layout", ["nchw", "nhwc"])
+@pytest.mark.parametrize("r", [1, 2, 3, 4, 5, 6, 7])
+def test_local_corr_every_radius_fp32_vs_oracle(r, layout):
+    """Every radius on the any-layout kernel (nchw) and the fp32 channels-last kernel (nhwc), coherent and incoherent tiles in one
+    launch.  30 x 34 leaves partial tiles on both axes for every tile size (8x8, 8x4, 4x4), and its 1 020 pixels exceed the largest
+    staged-box capacity of local_corr.hip (704 rows), so a tile of the adversarial block cannot stay on the shared-box path."""
+    f0, f1, flow, ref = _oracle_lc_radius(r)
+    a, b = f0.to(DEV), f1.to(DEV)
+    if layout == "nhwc":
+        a, b = a.contiguous(memory_format=torch.channels_last), b.contiguous(memory_format=torch.channels_last)
+    out = _ops().local_correlation(a, b, r, flow=flow.to(DEV))
+    assert out.shape == ref.shape
+    assert maxerr(out, ref) < 5e-5
+
+
 _ORACLE_LC = {}
 
 
@@ -122,7 +155,7 @@ def test_local_corr_16bit_kernels_vs_oracle_at_the_five_call_shapes(shape, dtype
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("shape", [(2, 512, 40, 40, 7), (1, 512, 70, 70, 3), (1, 256, 140, 140, 2), (1, 64, 37, 53, 2), (2, 32, 21, 18, 3),
-                                   (1, 96, 30, 44, 7), (1, 256, 216, 216, 2)])
+                                   (1, 96, 30, 44, 7), (1, 256, 216, 216, 2), (1, 32, 30, 34, 4), (1, 32, 30, 34, 5), (1, 64, 30, 34, 6)])
 @pytest.mark.parametrize("kind", ["coherent", "adversarial", "mixed"])
 def test_local_corr_matrix_core_path_vs_fp32_kernel(shape, kind, dtype):
     """16-bit channels-last inputs take the MFMA / per-pixel-patch kernel; the fp32 kernel (checked against the oracle
