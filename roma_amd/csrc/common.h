@@ -6,19 +6,9 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdint>
-#include "../../include/roma_hip.h"
+#include "error.h"
 
 namespace roma {
-
-void set_error(const char* fmt, ...);
-
-#define ROMA_REQUIRE(cond, code, ...)            \
-  do {                                           \
-    if (!(cond)) {                               \
-      ::roma::set_error(__VA_ARGS__);            \
-      return (code);                             \
-    }                                            \
-  } while (0)
 
 #define ROMA_CHECK_LAUNCH()                                           \
   do {                                                                \

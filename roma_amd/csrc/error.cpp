@@ -1,7 +1,7 @@
 // Thread-local error string + ABI version for libroma_hip.so.
 #include <cstdarg>
 #include <cstdio>
-#include "../../include/roma_hip.h"
+#include "error.h"
 
 namespace roma {
 static thread_local char g_err[512] = "";

@@ -1,7 +1,8 @@
 """JPEG decoding for match() on file paths (matcher.py:606-637, 667-676: `Image.open(path).convert("RGB")`).
 Host part (roma_jpeg_info / roma_jpeg_entropy_decode, no GPU) + the numpy restatement of libjpeg's reconstruction
 (oracle/jpeg_oracle.py) against PIL itself: bit-identical — that pins the restatement; the GPU test then holds roma_jpeg_reconstruct
-to the same images."""
+to the same images.  The host part reads bytes from outside, so malformed streams (crafted ones and a seeded mutation sweep) are held
+to a known return code and to the blocks roma_jpeg_info announced, with a guard band behind the coefficient array."""
 import glob
 import io
 import os
@@ -17,7 +18,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "assets", "*.jpg")))
 
 
-def _host_decode(data):
+GUARD, SENTINEL = 1024, 0x5A5A                                  # blocks behind the coefficient array that no call may touch, and what they hold
+OK_CODES = (0, _lib.ROMA_E_ARG, _lib.ROMA_E_UNSUPPORTED)
+
+
+def _host_decode(data, guard=0):
     lib = _lib.load()
     buf = np.frombuffer(data, dtype=np.uint8)
     info = np.zeros(8, np.int32)
@@ -25,9 +30,12 @@ def _host_decode(data):
     if rc != 0:
         return rc, None, None, None
     nb = int(info[4]) * int(info[5]) + 2 * int(info[6]) * int(info[7])
-    coef = np.zeros((nb, 64), np.int16)
+    room = np.full((nb + guard, 64), SENTINEL, np.int16)
+    coef = room[:nb]
+    coef[:] = 0
     qt = np.zeros((3, 64), np.uint16)
     rc = lib.roma_jpeg_entropy_decode(buf.ctypes.data, len(data), coef.ctypes.data, qt.ctypes.data)
+    assert (room[nb:] == SENTINEL).all(), "roma_jpeg_entropy_decode wrote behind the blocks roma_jpeg_info announced"
     return rc, info, coef, qt
 
 
@@ -94,6 +102,90 @@ def test_streams_outside_the_supported_subset_are_refused_not_misdecoded():
     data = open(ASSETS[0], "rb").read()
     rc, *_ = _host_decode(data[:600])                           # truncated inside the tables
     assert rc < 0
+
+
+def _segments(data):
+    """(marker, offset of its 0xFF, offset behind the segment) of every marker segment up to EOI, stepping over the entropy-coded data"""
+    out, i = [], 2
+    while i + 4 <= len(data) and data[i:i + 2] != b"\xff\xd9":
+        m = data[i + 1]
+        if data[i] != 0xFF or m in (0x00, 0xFF) or 0xD0 <= m <= 0xD7:
+            i += 1
+            continue
+        end = i + 2 + int.from_bytes(data[i + 2:i + 4], "big")
+        out.append((m, i, end))
+        i = end
+    return out
+
+
+def _encode(arr, **kw):
+    bio = io.BytesIO()
+    Image.fromarray(arr).save(bio, "JPEG", **kw)
+    return bio.getvalue()
+
+
+def _pattern(h, w):
+    return ((np.arange(h * w * 3) * 37) % 251).astype(np.uint8).reshape(h, w, 3)
+
+
+def _small_streams():
+    """The streams the mutation sweep starts from: few blocks, so that a case is two short calls; interleaved 4:2:0 and 4:2:2 baseline
+    scans and the progressive scan types with restart markers in them."""
+    syn = _synthetic_jpegs()
+    return {"tiny": syn["tiny"], "422_tiny": syn["422_tiny"],
+            "prog_rst_16": _encode(_pattern(16, 16), progressive=True, subsampling=0, quality=90, restart_marker_blocks=2)}
+
+
+def _crafted_streams():
+    """name -> (stream, the call that must return ROMA_E_ARG): the malformed streams that wrote out of bounds before the host stage
+    rejected them.  Each differs from a stream that decodes in the one respect its name gives."""
+    base = _encode(_pattern(24, 40), subsampling=2, quality=85)
+    prog = _encode(_pattern(32, 32), progressive=True, quality=85)
+    out = {"dht_oversubscribed": (b"\xff\xd8\xff\xc4" + (2 + 17 + 255).to_bytes(2, "big") + bytes([0, 255] + [0] * 15) + bytes(range(255)), "info")}
+    _, o, end = next(s for s in _segments(base) if s[0] == 0xC4)   # the first DHT segment, one value longer than its counts announce
+    out["dht_counts_one_short"] = (base[:o + 2] + (end - o - 2 + 1).to_bytes(2, "big") + base[o + 4:end] + b"\0" + base[end:], "info")
+    _, o, end = next(s for s in _segments(prog) if s[0] == 0xC2)
+    sof = bytearray(prog[o:end])
+    sof[5:9] = (1024).to_bytes(2, "big") * 2                      # height, width
+    ac = next(s[1] for s in _segments(prog) if s[0] == 0xDA and prog[s[2] - 3] > 0)   # the first scan with Ss > 0
+    out["second_sof"] = (prog[:ac] + bytes(sof) + prog[ac:], "entropy")
+    _, o, end = next(s for s in _segments(base) if s[0] == 0xDA)
+    for name, sel in (("dc_selector_7", 0x70), ("ac_selector_7", 0x07)):
+        out[name] = (base[:o + 6] + bytes([sel]) + base[o + 7:], "info")   # FF DA, length, Ns, component id, selectors
+    return out
+
+
+def test_crafted_streams_are_rejected_inside_the_buffer():
+    lib = _lib.load()
+    streams = _crafted_streams()
+    assert sorted(streams) == ["ac_selector_7", "dc_selector_7", "dht_counts_one_short", "dht_oversubscribed", "second_sof"]
+    for name, (data, call) in streams.items():
+        rc, info, _, _ = _host_decode(data, guard=GUARD)         # asserts the guard band itself
+        assert rc == _lib.ROMA_E_ARG, (name, rc, lib.roma_last_error())
+        assert (info is None) == (call == "info"), name          # the call that rejects it
+    assert tuple(_host_decode(streams["second_sof"][0])[1][:2]) == (32, 32)
+
+
+def test_mutated_streams_return_a_known_code_inside_the_buffer():
+    """2 000 seeded cases per small stream, 1-3 bytes behind the first SOF segment overwritten with random values (the frame, and so the
+    buffer sized from the intact stream, stays what it was): both host calls return 0, ROMA_E_ARG or ROMA_E_UNSUPPORTED, and the
+    guard band behind the coefficient array comes back intact."""
+    lib = _lib.load()
+    for seed, (name, data) in enumerate(_small_streams().items()):
+        rc, _, coef, _ = _host_decode(data)
+        assert rc == 0, name
+        nb, first = coef.shape[0], next(s[2] for s in _segments(data) if s[0] in (0xC0, 0xC1, 0xC2))
+        rng = np.random.default_rng(seed)
+        room, qt, info = np.empty((nb + GUARD, 64), np.int16), np.zeros((3, 64), np.uint16), np.zeros(8, np.int32)
+        for case in range(2000):
+            buf = np.frombuffer(data, dtype=np.uint8).copy()
+            k = int(rng.integers(1, 4))
+            buf[rng.integers(first, len(buf), size=k)] = rng.integers(0, 256, size=k)
+            room[:] = SENTINEL
+            rc_info = lib.roma_jpeg_info(buf.ctypes.data, len(buf), info.ctypes.data)
+            rc_dec = lib.roma_jpeg_entropy_decode(buf.ctypes.data, len(buf), room.ctypes.data, qt.ctypes.data)
+            assert rc_info in OK_CODES and rc_dec in OK_CODES, (name, case, rc_info, rc_dec)
+            assert (room[nb:] == SENTINEL).all(), (name, case)
 
 
 @pytest.mark.gpu
