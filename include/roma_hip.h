@@ -388,6 +388,33 @@ int roma_refine_fundamental(const double* xa, const double* xb, const double* F_
                             double threshold, int iters, double* F, unsigned char* mask, double* cost, int* count, int* steps,
                             void* stream);
 
+/* Two-view triangulation of matches under a known relative pose (csrc/triangulate.hip) — what a caller does with
+ * the (R, t) of roma_recover_pose / roma_refine_pose: a point cloud of the sampled matches, or a depth map per image from every row of
+ * the dense warp.  Convention of roma_recover_pose: x_B ~ K_B (R X_A + t).  Points are expressed in camera A's frame, in units of
+ * |t|: with the unit t of roma_recover_pose, depths are in baselines.
+ *   m: (P,N,4) fp32 device, contiguous, 16-byte aligned, rows [xa, ya, xb, yb] — the layout of the warp of match(), of what sample()
+ *     returns, of cat(kptsA, kptsB);
+ *   to_px: 8 floats in HOST memory, read during the call, or NULL: (sx_A, ox_A, sy_A, oy_A, sx_B, ox_B, sy_B, oy_B), pixel = s * c + o.
+ *     NULL: the rows are pixels already.  For the normalised coordinates of a warp: (W_A/2, W_A/2, H_A/2, H_A/2, W_B/2, ...);
+ *   Ka, Kb: (P,3,3) fp64 intrinsics as roma_recover_pose; R: (P,3,3) fp64; t: (P,3) fp64, of any length;
+ *   mask_in: (P,N) uint8 or NULL (= all); method: 0 = optimal, 1 = midpoint; max_reproj: pixels, +inf = no gate; max_cos_parallax:
+ *     1 = no gate (the caller turns a smallest parallax angle into its cosine).
+ * Per pair, in fp64: F = K_B^-T [t]x R K_A^-1 scaled to unit Frobenius norm and the two inverse intrinsics; then, per match, in fp32:
+ *   method 0: Lindstrom's closed-form two-step correction (niter2) in pixel space moves (x_A, x_B) by the smallest |d_A|^2 + |d_B|^2
+ *     onto x_B^T F x_A = 0; the corrected rays a, b meet, lambda_B b = lambda_A R a + t, X_A = lambda_A a, the depths are lambda_A and
+ *     lambda_B, reproj = sqrt(|d_A|^2 + |d_B|^2);
+ *   method 1: the same depths on the uncorrected rays; X_A is the midpoint of the two closest points, the depths are its z in A and
+ *     in B, reproj is the root of the sum over both images of the squared pixel distance from its projection to the match;
+ *   cos_parallax = (R a . b) / (|R a| |b|).
+ * Outputs, device, each may be NULL but not all: points (P,N,3) fp32; depth_a, depth_b, reproj, cos_parallax (P,N) fp32; valid (P,N)
+ * uint8 = input finite, mask_in set, solution finite, both depths > 0, reproj <= max_reproj, cos_parallax <= max_cos_parallax.  Every
+ * requested element is written: exact zeros everywhere for a match whose input or solution is not finite (a singular K, t = 0 or
+ * parallel rays among them), the computed values for any other match, valid or not; never NaN or inf.  An output does not depend on
+ * which other outputs are requested, nor a pair on the other pairs.  One launch, no workspace, no atomics, no host synchronisation. */
+int roma_triangulate(const float* m, const float* to_px, const double* Ka, const double* Kb, const double* R, const double* t,
+                     const unsigned char* mask_in, int P, int N, int method, float max_reproj, float max_cos_parallax, float* points,
+                     float* depth_a, float* depth_b, float* reproj, float* cos_parallax, unsigned char* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,8 @@ SIGNATURES = {
                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "roma_refine_fundamental": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p],
+    "roma_triangulate": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
+                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 _RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long, "roma_essential_workspace": c_long}
 

@@ -26,10 +26,15 @@ poselib.estimate_relative_pose, the call of the reference's PoseLib benchmark
 `refine_fundamental` is the same polish for the uncalibrated path (csrc/fundamental_refine.hip): Levenberg-Marquardt on the truncated
 Sampson cost in pixels over the rank-2 manifold, what cv2.findFundamentalMat runs after consensus.  `find_fundamental` and
 `estimate_pose_uncalibrated` run it on request (refine_iters > 0).
+
+`triangulate` turns matches and a relative pose into 3-D points, depths, reprojection errors and a validity flag per match
+(csrc/triangulate.hip: fp32 per match from pair constants prepared in fp64; Lindstrom's optimal correction or the midpoint), and
+`depth_from_warp` does so for every row of the dense warp of match() in one launch: a depth map per image.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -534,3 +539,150 @@ def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=100
         "T_A": T[:, 0].clone(),
         "T_B": T[:, 1].clone(),
     }
+
+
+# ------------------------------------------------------------------------------------------------------------ triangulation
+_METHODS = {"optimal": 0, "midpoint": 1}
+
+
+class Triangulation:
+    """What triangulate returns: points (..., N, 3) in camera A's frame, depth_A, depth_B (the z in each camera), reproj_error
+    (pixels), cos_parallax — fp32 —, valid (bool); all (..., N) device tensors."""
+    __slots__ = ("points", "depth_A", "depth_B", "reproj_error", "cos_parallax", "valid")
+
+    def __init__(self, points, depth_A, depth_B, reproj_error, cos_parallax, valid):
+        self.points, self.depth_A, self.depth_B = points, depth_A, depth_B
+        self.reproj_error, self.cos_parallax, self.valid = reproj_error, cos_parallax, valid
+
+    def __repr__(self):
+        return f"Triangulation(points={tuple(self.points.shape)}, device={self.points.device})"
+
+
+class WarpDepth:
+    """What depth_from_warp returns: depth_A (..., H, W) with valid_A, depth_B (..., H, W) with valid_B (None for a warp that is not
+    symmetric) — fp32, 0 where not valid —, points (..., H, W or 2W, 3) in camera A's frame and valid (..., H, W or 2W) of every row."""
+    __slots__ = ("depth_A", "valid_A", "depth_B", "valid_B", "points", "valid")
+
+    def __init__(self, depth_A, valid_A, depth_B, valid_B, points, valid):
+        self.depth_A, self.valid_A, self.depth_B, self.valid_B, self.points, self.valid = depth_A, valid_A, depth_B, valid_B, points, valid
+
+    def __repr__(self):
+        return f"WarpDepth(depth_A={tuple(self.depth_A.shape)}, points={tuple(self.points.shape)}, device={self.points.device})"
+
+
+def _gates(method, max_reproj_error, min_parallax_deg):
+    """-> (method code, max_reproj in pixels, max_cos_parallax), checked before anything looks at a tensor"""
+    if method not in _METHODS:
+        raise ValueError(f"unknown method {method!r}: 'optimal' or 'midpoint'")
+    max_reproj = float("inf") if max_reproj_error is None else float(max_reproj_error)
+    if not max_reproj >= 0:
+        raise ValueError(f"max_reproj_error must be >= 0 pixels or None, got {max_reproj_error}")
+    deg = float(min_parallax_deg)
+    if not 0.0 <= deg <= 180.0:
+        raise ValueError(f"min_parallax_deg must be in [0, 180], got {min_parallax_deg}")
+    return _METHODS[method], max_reproj, (1.0 if deg == 0.0 else math.cos(math.radians(deg)))
+
+
+def _pose(R, t, P, single, device):
+    """(3,3) / (3,) or (P,3,3) / (P,3), tensor or numpy -> contiguous (P,3,3), (P,3) fp64 on the device"""
+    if not torch.is_tensor(R):
+        R = torch.as_tensor(R, dtype=torch.float64).to(device)
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(t, dtype=torch.float64).to(device)
+    _need_gpu(R, t)
+    if (R.shape != (3, 3) or t.shape != (3,)) and (single or R.shape != (P, 3, 3) or t.shape != (P, 3)):
+        raise ValueError(f"R {tuple(R.shape)}, t {tuple(t.shape)}: expected (3,3) and (3,)" + ("" if single else f", or ({P},3,3) and ({P},3)"))
+    return R.to(torch.float64).expand(P, 3, 3).contiguous(), t.to(torch.float64).expand(P, 3).contiguous()
+
+
+def _triangulate(m, to_px, R, t, K_A, K_B, single, code, max_reproj, max_cos, mask, want_all=True):
+    """m: (P,N,4) device tensor of any float dtype -> the six outputs of roma_triangulate, batched"""
+    P, N = m.shape[0], m.shape[1]
+    if P < 1 or N < 1:
+        raise ValueError(f"no matches: {P} pairs of {N}")
+    m = m.to(torch.float32).contiguous()
+    Ka, Kb = _intrinsics(K_A, P, m.device, "K_A"), _intrinsics(K_B, P, m.device, "K_B")
+    Rp, tp = _pose(R, t, P, single, m.device)
+    mk = None
+    if mask is not None:
+        _need_gpu(mask)
+        mk = mask.reshape(P, N).to(torch.uint8).contiguous()
+    f32 = dict(dtype=torch.float32, device=m.device)
+    points = torch.empty((P, N, 3), **f32)
+    depth_a, depth_b = torch.empty((P, N), **f32), torch.empty((P, N), **f32)
+    reproj, cosp = (torch.empty((P, N), **f32), torch.empty((P, N), **f32)) if want_all else (None, None)
+    valid = torch.empty((P, N), dtype=torch.uint8, device=m.device)
+    px = None if to_px is None else (ctypes.c_float * 8)(*to_px)
+    check(_lib.load().roma_triangulate(m.data_ptr(), None if px is None else ctypes.cast(px, ctypes.c_void_p), Ka.data_ptr(), Kb.data_ptr(),
+                                       Rp.data_ptr(), tp.data_ptr(), None if mk is None else mk.data_ptr(), P, N, code, max_reproj, max_cos,
+                                       points.data_ptr(), depth_a.data_ptr(), depth_b.data_ptr(), None if reproj is None else reproj.data_ptr(),
+                                       None if cosp is None else cosp.data_ptr(), valid.data_ptr(), _stream()), "roma_triangulate")
+    return points, depth_a, depth_b, reproj, cosp, valid.bool()
+
+
+def triangulate(x_A, x_B, R, t, K_A, K_B, *, method="optimal", max_reproj_error=None, min_parallax_deg=0.0, mask=None):
+    """3-D points of pixel correspondences x_A <-> x_B under a known relative pose — of recover_pose / estimate_pose / refine_pose —
+    in their convention x_B ~ K_B (R X_A + t) (csrc/triangulate.hip).  Points are in camera A's frame and in units of |t|: with the
+    unit t of recover_pose, depths come out in baselines.
+    x_A, x_B: (N,2) with R (3,3), t (3,), or (P,N,2) with (P,3,3), (P,3) or one shared pose; any float dtype on the device (the kernel
+    computes in fp32 from pair constants prepared in fp64).  K_A, K_B: (3,3) shared or (P,3,3), as find_essential.
+    method "optimal": Lindstrom's closed-form correction moves the match by the smallest pixel distance onto the epipolar line pair,
+    the corrected rays meet in the point, reproj_error = that distance, sqrt(|d_A|^2 + |d_B|^2).  "midpoint": the middle of the two
+    rays' closest points, reproj_error the root of the sum over both images of its squared reprojection distance; cheaper, never
+    more accurate.  cos_parallax is the cosine of the angle between the two rays.
+    valid: the match is finite, `mask` (bool / uint8, optional) is set, the solution is finite, both depths are positive,
+    reproj_error <= max_reproj_error (pixels; None = no gate) and the parallax is at least min_parallax_deg.  Matches that are not
+    finite, or have no finite solution (parallel rays, t = 0, a singular K), get zeros in every field; the others their values,
+    valid or not.  Returns a Triangulation: points (N,3) / (P,N,3), depth_A, depth_B, reproj_error, cos_parallax fp32, valid bool.
+    No host synchronisation: the call can be captured in a hipGraph."""
+    code, max_reproj, max_cos = _gates(method, max_reproj_error, min_parallax_deg)
+    _need_gpu(x_A, x_B)
+    if x_A.shape != x_B.shape or x_A.dim() not in (2, 3) or x_A.shape[-1] != 2:
+        raise ValueError(f"expected two (N,2) or (P,N,2) tensors of pixel coordinates, got {tuple(x_A.shape)} and {tuple(x_B.shape)}")
+    if not (x_A.is_floating_point() and x_B.is_floating_point()):
+        raise ValueError(f"pixel coordinates must be floating point, got {x_A.dtype} and {x_B.dtype}")
+    single = x_A.dim() == 2
+    P, N = (1, x_A.shape[0]) if single else (x_A.shape[0], x_A.shape[1])
+    if mask is not None and mask.shape != ((N,) if single else (P, N)):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
+    m = torch.cat((x_A.reshape(P, N, 2).float(), x_B.reshape(P, N, 2).float()), -1)
+    out = _triangulate(m, None, R, t, K_A, K_B, single, code, max_reproj, max_cos, mask)
+    return Triangulation(*((o[0] for o in out) if single else out))
+
+
+def depth_from_warp(warp, certainty, R, t, K_A, K_B, H_A, W_A, H_B=None, W_B=None, *, certainty_thresh=0.05, method="optimal",
+                    max_reproj_error=None, min_parallax_deg=0.0, mask=None, symmetric=True):
+    """Dense depth maps of both images from the warp of match() and a relative pose (of estimate_pose on its sampled matches, say).
+    warp: (H, 2W, 4) symmetric — the left half rows are [grid_A, predicted x_B], the right half [predicted x_A, grid_B] — or
+    (P, H, 2W, 4) of match_tensors, in normalised coordinates; every row is an (x_A, x_B) match, and the whole array goes through
+    triangulate's kernel in one launch, which maps it to pixels as to_pixel_coordinates(warp, H_A, W_A, H_B, W_B) does (H_B, W_B
+    default to H_A, W_A).  K_A, K_B are the intrinsics at those image sizes; R, t, method, max_reproj_error, min_parallax_deg as
+    triangulate.  A row counts only where certainty (H, 2W) > certainty_thresh and `mask` (same shape, optional — e.g. of
+    RegressionMatcher.conf_from_fb_consistency) is set.  symmetric=False: the warp of a matcher that is not symmetric, (H, W, 4), every
+    row [grid_A, predicted x_B]; it gives the A half only (the shape cannot tell the two apart, and looking at the grid would
+    synchronise with the host).
+    Returns a WarpDepth: depth_A (H,W) = z in camera A of the left half with valid_A, depth_B (H,W) = z in camera B of the right
+    half with valid_B, 0 where not valid; points (H, 2W, 3) in A's frame and valid (H, 2W) of every row; a leading P if given."""
+    code, max_reproj, max_cos = _gates(method, max_reproj_error, min_parallax_deg)
+    _need_gpu(warp, certainty, mask)
+    if warp.dim() not in (3, 4) or warp.shape[-1] != 4 or not warp.is_floating_point():
+        raise ValueError(f"expected a floating-point warp (H, W2, 4) or (P, H, W2, 4), got {tuple(warp.shape)} {warp.dtype}")
+    single = warp.dim() == 3
+    P, H, W2 = (1,) + tuple(warp.shape[:2]) if single else tuple(warp.shape[:3])
+    for name, v in (("certainty", certainty), ("mask", mask)):
+        if v is not None and v.shape != warp.shape[:-1]:
+            raise ValueError(f"{name} {tuple(v.shape)} does not match the warp {tuple(warp.shape)}")
+    H_B, W_B = H_A if H_B is None else H_B, W_A if W_B is None else W_B
+    to_px = (W_A / 2, W_A / 2, H_A / 2, H_A / 2, W_B / 2, W_B / 2, H_B / 2, H_B / 2)
+    keep = certainty > certainty_thresh
+    if mask is not None:
+        keep = keep & (mask != 0)
+    points, da, db, _, _, valid = _triangulate(warp.reshape(P, H * W2, 4), to_px, R, t, K_A, K_B, single, code, max_reproj, max_cos,
+                                               keep.reshape(P, H * W2), want_all=False)
+    points, valid = points.reshape(P, H, W2, 3), valid.reshape(P, H, W2)
+    da, db = torch.where(valid, da.reshape(P, H, W2), 0.0), torch.where(valid, db.reshape(P, H, W2), 0.0)
+    if symmetric and W2 % 2:
+        raise ValueError(f"a symmetric warp has an even width, got {W2}; pass symmetric=False for an (H, W, 4) warp")
+    W = W2 // 2 if symmetric else W2
+    res = (da[..., :W], valid[..., :W], db[..., W:] if symmetric else None, valid[..., W:] if symmetric else None, points, valid)
+    return WarpDepth(*((None if o is None else o[0]) for o in res) if single else res)

@@ -594,6 +594,25 @@ class RegressionMatcher(nn.Module):
             return (iA, iB) if return_inds else (x_A[iA], x_B[iB])
         return torch.cat((iA, iB), dim=-1) if return_inds else torch.cat((x_A[iA], x_B[iB]), dim=-1)
 
+    def conf_from_fb_consistency(self, flow_forward, flow_backward, th=2):
+        """matcher.py:530-551: forward-backward consistency of two dense flows, (H,W,2) or (B,H,W,2) in normalised coordinates.  A
+        pixel is consistent when the backward flow, sampled bilinearly (zero padding) where the forward flow points, leads back to
+        within `th` pixels of it — th_n = 2 th / max(H, W) in normalised units, the pixel grid from linspace(-1 + 1/W, 1 - 1/W, W).
+        Returns the mask as floats, with the batch dimension only if it was given.  The sampling is ops.warp_bilinear (the kernel
+        of the refiners), so the flows must live on the device; e.g. warp[:, :W, 2:] and warp[:, W:, :2] of a symmetric match, and
+        the result as `mask` of geometry.depth_from_warp."""
+        has_batch = flow_forward.dim() != 3
+        if not has_batch:
+            flow_forward, flow_backward = flow_forward[None], flow_backward[None]
+        H, W = flow_forward.shape[-3:-1]
+        th_n = 2 * th / max(H, W)
+        dev = flow_forward.device
+        coords = torch.stack(torch.meshgrid(torch.linspace(-1 + 1 / W, 1 - 1 / W, W, device=dev),
+                                            torch.linspace(-1 + 1 / H, 1 - 1 / H, H, device=dev), indexing="xy"), dim=-1)
+        coords_fb = ops.warp_bilinear(flow_backward.permute(0, 3, 1, 2), flow_forward.permute(0, 3, 1, 2)).permute(0, 2, 3, 1)
+        in_th = ((coords - coords_fb).norm(dim=-1) < th_n).float()
+        return in_th if has_batch else in_th[0]
+
     # -- match -----------------------------------------------------------------------------------
     @torch.inference_mode()
     def match_tensors(self, A_lo, B_lo, A_hi=None, B_hi=None):
