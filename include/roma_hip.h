@@ -72,6 +72,25 @@ int roma_disp_emb(const float* flow, const float* weight, const float* bias, voi
  * (matcher.py:397-399): not here; see roma_flow_update. */
 int roma_interp_bilinear(const float* x, float* y, int N, int Hi, int Wi, int Ho, int Wo, void* stream);
 
+/* The same resize of TWO maps of one size in one launch — matcher.py:408-417, where the decoder upsamples flow and certainty
+ * between levels: x0 (N0,Hi,Wi) -> y0 (N0,Ho,Wo) and x1 (N1,Hi,Wi) -> y1 (N1,Ho,Wo).  Every element is computed as by
+ * roma_interp_bilinear. */
+int roma_interp_bilinear_pair(const float* x0, float* y0, int N0, const float* x1, float* y1, int N1, int Hi, int Wi, int Ho, int Wo,
+                              void* stream);
+
+/* Input assembly of a ConvRefiner — matcher.py:109-120 and the channel padding of the concat buffer, in one launch:
+ *   buf[.., C:2C]      = grid_sample(src, flow)           as roma_warp_bilinear, with src_batch_shift
+ *   buf[.., 2C:2C+E]   = Conv1x1(2->E)(gain * (flow - identity_grid))   as roma_disp_emb
+ *   buf[.., D:pitch]   = 0
+ * buf: (B,H,W,pitch) channels-last of `dtype` (fp16 / bf16); src: (B,Hs,Ws,src_pitch) channels-last, C channels used, and may be
+ * buf itself (x in channels [0, C), sampled with a batch shift); flow (B,2,H,W) fp32; weight (E,2), bias (E) fp32.  Every element
+ * has the bits the two separate calls give.  Channels [0, C) are never written.  Channels [2C+E, D) are left alone except those that
+ * share a 16-byte packet with channel D, which are zeroed: the local correlation, written afterwards, owns that slice.
+ * Supported: C and E multiples of 8, or (C, E, D, pitch) = (9, 6, 24, 24) with src_pitch >= 16; pitches multiples of 8. */
+int roma_refiner_assemble(const void* src, const float* flow, const float* weight, const float* bias, void* buf, int B, int C, int E,
+                          int D, int pitch, int Hs, int Ws, int H, int W, int src_pitch, int src_batch_shift, float gain, int dtype,
+                          void* stream);
+
 /* Decoder.forward update step — matcher.py:397-402:
  *   flow[b,0] += ins*delta[b,0]/(4*Wf); flow[b,1] += ins*delta[b,1]/(4*Hf); cert[b] += delta[b,2]
  *   delta: (B,3,H,W) fp32 planar (the refiner's out_conv result); cert may be NULL-initialised via cert_in==NULL (=0). */
@@ -246,6 +265,14 @@ int roma_refiner_head(const void* x, const float* wo, const float* bo, float* fl
  *   (in, out), bias (C) fp32.  C a multiple of 8 (fp16/bf16) or 4 (fp32), C <= 32. */
 int roma_pointwise_small(const void* x, const float* wt, const float* bias, void* y, long M, int C, int dtype,
                          int x_pitch, int y_pitch, void* stream);
+
+/* The decoder's folded 1x1 projection (Conv2d + BatchNorm, matcher.py:366-371) at the two finest scales, as a streaming kernel:
+ *   y[m][n] = bias[n] + sum_k x[m][k] * wt[n][k],  n < N;   (K, N) = (64, 9) or (128, 64), fp16 / bf16, fp32 accumulation.
+ *   x: (M, x_pitch) channels-last pixels; y: (M, y_pitch) rows of which only columns [0, N) are written (a slice of the refiner's
+ *   concat buffer); wt: (N rounded up to 16, K) of `dtype`, out-major, rows >= N zero; bias: (N rounded up to 16) fp32.
+ *   Pitches multiples of 8, bases 16-byte aligned. */
+int roma_project_skinny(const void* x, const void* wt, const float* bias, void* y, long M, int K, int N, int dtype, int x_pitch,
+                        int y_pitch, void* stream);
 
 /* Residual add (+ LayerScale) fused with the following LayerNorm — the seam between two transformer half-blocks
  * (transformer/layers/block.py:87-107) and the fp32 token stream of the decoder transformer under autocast

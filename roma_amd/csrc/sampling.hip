@@ -224,6 +224,191 @@ __global__ __launch_bounds__(256) void interp_kernel(const float* __restrict__ x
   }
 }
 
+// Two maps of one size in one launch (the decoder upsamples flow and certainty between levels): planes [0, N0) are x0 -> y0, planes
+// [N0, N0 + N1) are x1 -> y1; per element the arithmetic of interp_kernel.
+__global__ __launch_bounds__(256) void interp_pair_kernel(const float* __restrict__ x0, float* __restrict__ y0, int N0,
+                                                          const float* __restrict__ x1, float* __restrict__ y1, int N1, int Hi, int Wi,
+                                                          int Ho, int Wo) {
+  const size_t total = (size_t)(N0 + N1) * Ho * Wo;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int xo = (int)(i % Wo);
+    const int yo = (int)((i / Wo) % Ho);
+    const int n = (int)(i / ((size_t)Wo * Ho));
+    int ya, yb, xa, xb;
+    float ly, lx;
+    interp_src(yo, Hi, Ho, ya, yb, ly);
+    interp_src(xo, Wi, Wo, xa, xb, lx);
+    const bool second = n >= N0;
+    const float* p = (second ? x1 + (size_t)(n - N0) * Hi * Wi : x0 + (size_t)n * Hi * Wi);
+    const float top = (1.f - lx) * p[(size_t)ya * Wi + xa] + lx * p[(size_t)ya * Wi + xb];
+    const float bot = (1.f - lx) * p[(size_t)yb * Wi + xa] + lx * p[(size_t)yb * Wi + xb];
+    float* q = second ? y1 + (i - (size_t)N0 * Ho * Wo) : y0 + i;
+    *q = (1.f - ly) * top + ly * bot;
+  }
+}
+
+// One displacement-embedding element as 16 bits, rounded the way disp_emb_kernel's `from_f32<T>(fma(w1, dy, fma(w0, dx, b)))` is: for
+// fp16 hipcc compiles that scalar expression to v_fma_mixlo_f16 (the outer multiply-add and the conversion in ONE rounding), but
+// several of them side by side to packed fp32 multiply-adds and a packed conversion (two roundings, one fp16 ulp apart for about one
+// element in 10^4).  The kernels that compute eight or six elements per thread name the instruction, so that they keep the bits.
+template <typename T>
+__device__ __forceinline__ uint32_t emb_bits(float w0, float w1, float b, float dx, float dy) {
+  const float inner = __builtin_fmaf(w0, dx, b);
+  if constexpr (__is_same(T, half_t)) {
+    uint32_t r;                                                   // all three sources fp32 (op_sel_hi clear); writes bits [15:0] only
+    asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(r) : "v"(w1), "v"(dy), "v"(inner));
+    return r & 0xffffu;
+  } else {
+    return __builtin_bit_cast(uint16_t, from_f32<T>(__builtin_fmaf(w1, dy, inner)));
+  }
+}
+
+// ---- One launch per refiner level for everything of the concat buffer's pixel that is neither x nor the local correlation: the warp
+// of y at `flow` into channels [C, 2C), the displacement embedding into [2C, 2C + E) and zeros into the padding [D, Dp).  The flow is
+// read and corners() evaluated once per thread; the per-element expressions are those of warp_nhwc_kernel / warp_small_kernel /
+// disp_emb_kernel, rounded as there (emb_bits), so the bits are theirs.
+// Channels [0, C) are never written: with y = x and a batch shift other threads are gathering
+// them from this very buffer. ----
+struct AsmParams {
+  const void* src;      // y: channels-last (B,Hs,Ws,src_pitch); may be the buffer itself
+  const float* flow;    // (B,2,H,W)
+  const float* weight;  // (E,2)
+  const float* bias;    // (E)
+  void* buf;            // (B,H,W,pitch)
+  int B, C, E, D, pitch, Hs, Ws, H, W, src_pitch, src_shift;
+  float gain;
+};
+
+// C and E whole packets.  One thread per (pixel, packet): C/8 warp packets, E/8 embedding packets, then the zero packets from the one
+// that holds channel D to the end of the pixel.  That first zero packet also covers the last channels of [2C + E, D) when D is not a
+// multiple of 8: local_correlation runs after this kernel on the same stream and writes that slice.
+template <typename T>
+__global__ __launch_bounds__(256) void assemble_packets_kernel(AsmParams p) {
+  static_assert(sizeof(T) == 2, "16-bit elements");
+  const int PW = p.C / 8, PE = p.E / 8, Z0 = p.D / 8;
+  const int PP = PW + PE + (p.pitch / 8 - Z0);
+  const size_t total = (size_t)p.B * p.H * p.W * PP;
+  const bool narrow = total <= 0x7fffffffu;                      // 32-bit index arithmetic wherever it is enough
+  const T* src = static_cast<const T*>(p.src);
+  T* buf = static_cast<T*>(p.buf);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    int k, x, y, b;
+    size_t pix;
+    if (narrow) {
+      const uint32_t i32 = (uint32_t)i, px = i32 / (uint32_t)PP, row = px / (uint32_t)p.W;
+      k = (int)(i32 - px * PP);
+      x = (int)(px - row * p.W);
+      b = (int)(row / (uint32_t)p.H);
+      y = (int)(row - (uint32_t)b * p.H);
+      pix = px;
+    } else {
+      k = (int)(i % PP);
+      pix = i / PP;
+      x = (int)(pix % p.W);
+      y = (int)((pix / p.W) % p.H);
+      b = (int)(pix / ((size_t)p.W * p.H));
+    }
+    const float fx = p.flow[((size_t)(b * 2 + 0) * p.H + y) * p.W + x];
+    const float fy = p.flow[((size_t)(b * 2 + 1) * p.H + y) * p.W + x];
+    T* d = buf + pix * p.pitch;
+    if (k < PW) {
+      const int Hs = p.Hs, Ws = p.Ws;
+      const Corner c = corners(fx, fy, Hs, Ws);
+      // the four taps: unconditional loads from clamped coordinates, masked through their weights (see warp_nhwc_kernel)
+      const T* base = src + (size_t)((b + p.src_shift) % p.B) * Hs * Ws * p.src_pitch + (size_t)k * 8;
+      const int xa = min(max(c.x0, 0), Ws - 1), xb = min(max(c.x0 + 1, 0), Ws - 1);
+      const int ya = min(max(c.y0, 0), Hs - 1), yb = min(max(c.y0 + 1, 0), Hs - 1);
+      const u32x4 v00 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xa) * p.src_pitch);
+      const u32x4 v01 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xb) * p.src_pitch);
+      const u32x4 v10 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xa) * p.src_pitch);
+      const u32x4 v11 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xb) * p.src_pitch);
+      const float w00 = c.v00 ? c.w00 : 0.f, w01 = c.v01 ? c.w01 : 0.f, w10 = c.v10 ? c.w10 : 0.f, w11 = c.v11 ? c.w11 : 0.f;
+      float f00[8], f01[8], f10[8], f11[8], acc[8];
+      unpack16<T>(v00, f00);
+      unpack16<T>(v01, f01);
+      unpack16<T>(v10, f10);
+      unpack16<T>(v11, f11);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        acc[e] = __builtin_fmaf(w11, f11[e], __builtin_fmaf(w10, f10[e], __builtin_fmaf(w01, f01[e], w00 * f00[e])));
+      *reinterpret_cast<u32x4*>(d + p.C + k * 8) = pack16<T>(acc);
+    } else if (k < PW + PE) {
+      const int e0 = (k - PW) * 8;
+      const float dx = p.gain * (fx - pix_center(x, p.W));
+      const float dy = p.gain * (fy - pix_center(y, p.H));
+      u32x4 v;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = e0 + 2 * j;
+        v[j] = emb_bits<T>(p.weight[2 * e], p.weight[2 * e + 1], p.bias[e], dx, dy) |
+               (emb_bits<T>(p.weight[2 * e + 2], p.weight[2 * e + 3], p.bias[e + 1], dx, dy) << 16);
+      }
+      *reinterpret_cast<u32x4*>(d + 2 * p.C + e0) = v;
+    } else {
+      *reinterpret_cast<u32x4*>(d + (Z0 + (k - PW - PE)) * 8) = u32x4{0, 0, 0, 0};
+    }
+  }
+}
+
+// The scale-1 pixel: C = 9, E = 6, D = pitch = 24 (48 bytes).  One thread per pixel writes channels [9, 24), bytes 18 .. 47 of the
+// pixel, as a 2-, a 4-, an 8- and a 16-byte store; every tap is the 16-byte packet of channels 0..7 plus the 32-bit word that holds
+// channel 8 (its upper half, channel 9 of the source pixel, is ignored: in the buffer itself another thread may be writing it).
+template <typename T>
+__global__ __launch_bounds__(256) void assemble_9_6_kernel(AsmParams p) {
+  static_assert(sizeof(T) == 2, "16-bit elements");
+  constexpr int C = 9, E = 6;
+  const size_t total = (size_t)p.B * p.H * p.W;
+  const T* src = static_cast<const T*>(p.src);
+  T* buf = static_cast<T*>(p.buf);
+  const int Hs = p.Hs, Ws = p.Ws;
+  for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < total; pix += (size_t)gridDim.x * blockDim.x) {
+    const uint32_t px = (uint32_t)pix, row = px / (uint32_t)p.W;    // the host refuses more than 2^31 pixels
+    const int x = (int)(px - row * p.W);
+    const int b = (int)(row / (uint32_t)p.H);
+    const int y = (int)(row - (uint32_t)b * p.H);
+    const float fx = p.flow[((size_t)(b * 2 + 0) * p.H + y) * p.W + x];
+    const float fy = p.flow[((size_t)(b * 2 + 1) * p.H + y) * p.W + x];
+    const Corner c = corners(fx, fy, Hs, Ws);
+    const T* base = src + (size_t)((b + p.src_shift) % p.B) * Hs * Ws * p.src_pitch;
+    const int xa = min(max(c.x0, 0), Ws - 1), xb = min(max(c.x0 + 1, 0), Ws - 1);
+    const int ya = min(max(c.y0, 0), Hs - 1), yb = min(max(c.y0 + 1, 0), Hs - 1);
+    const T* tap[4] = {base + ((size_t)ya * Ws + xa) * p.src_pitch, base + ((size_t)ya * Ws + xb) * p.src_pitch,
+                       base + ((size_t)yb * Ws + xa) * p.src_pitch, base + ((size_t)yb * Ws + xb) * p.src_pitch};
+    u32x4 v[4];
+    uint32_t v8[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {                               // unconditional, clamped: masked through the weights
+      v[t] = *reinterpret_cast<const u32x4*>(tap[t]);
+      v8[t] = *reinterpret_cast<const uint32_t*>(tap[t] + 8);
+    }
+    const float w00 = c.v00 ? c.w00 : 0.f, w01 = c.v01 ? c.w01 : 0.f, w10 = c.v10 ? c.w10 : 0.f, w11 = c.v11 ? c.w11 : 0.f;
+    float f[4][C];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      unpack16<T>(v[t], f[t]);
+      f[t][8] = to_f32(__builtin_bit_cast(T, (uint16_t)(v8[t] & 0xffffu)));
+    }
+    uint16_t o[C + E];
+#pragma unroll
+    for (int e = 0; e < C; ++e) {
+      float a = __builtin_fmaf(w11, f[3][e], __builtin_fmaf(w10, f[2][e], __builtin_fmaf(w01, f[1][e], w00 * f[0][e])));
+      asm("" : "+v"(a));                                         // warp_small_kernel rounds to fp32, then to T: no fused conversion here
+      o[e] = __builtin_bit_cast(uint16_t, from_f32<T>(a));
+    }
+    const float dx = p.gain * (fx - pix_center(x, p.W));
+    const float dy = p.gain * (fy - pix_center(y, p.H));
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+      o[C + e] = (uint16_t)emb_bits<T>(p.weight[2 * e], p.weight[2 * e + 1], p.bias[e], dx, dy);
+    T* d = buf + pix * p.pitch;                                  // 16-byte aligned: channel 9 is byte 18
+    auto pair = [&](int j) { return (uint32_t)o[j] | ((uint32_t)o[j + 1] << 16); };
+    *reinterpret_cast<uint16_t*>(d + 9) = o[0];
+    *reinterpret_cast<uint32_t*>(d + 10) = pair(1);
+    *reinterpret_cast<uint2*>(d + 12) = make_uint2(pair(3), pair(5));
+    *reinterpret_cast<u32x4*>(d + 16) = u32x4{pair(7), pair(9), pair(11), pair(13)};
+  }
+}
+
 __global__ __launch_bounds__(256) void flow_update_kernel(float* __restrict__ flow, float* __restrict__ cert,
                                                           const float* __restrict__ cert_in, const float* __restrict__ delta, int B,
                                                           int HW, float sx, float sy) {
@@ -310,6 +495,44 @@ extern "C" int roma_interp_bilinear(const float* x, float* y, int N, int Hi, int
   ROMA_REQUIRE(x && y, ROMA_E_ARG, "roma_interp_bilinear: null pointer");
   ROMA_REQUIRE(N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, ROMA_E_SHAPE, "roma_interp_bilinear: bad shape");
   hipLaunchKernelGGL(interp_kernel, dim3(grid_for((size_t)N * Ho * Wo)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, N, Hi, Wi, Ho, Wo);
+  ROMA_CHECK_LAUNCH();
+}
+
+extern "C" int roma_interp_bilinear_pair(const float* x0, float* y0, int N0, const float* x1, float* y1, int N1, int Hi, int Wi, int Ho,
+                                         int Wo, void* stream) {
+  ROMA_REQUIRE(x0 && y0 && x1 && y1, ROMA_E_ARG, "roma_interp_bilinear_pair: null pointer");
+  ROMA_REQUIRE(N0 > 0 && N1 > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, ROMA_E_SHAPE, "roma_interp_bilinear_pair: bad shape");
+  hipLaunchKernelGGL(interp_pair_kernel, dim3(grid_for((size_t)(N0 + N1) * Ho * Wo)), dim3(256), 0, static_cast<hipStream_t>(stream), x0, y0,
+                     N0, x1, y1, N1, Hi, Wi, Ho, Wo);
+  ROMA_CHECK_LAUNCH();
+}
+
+extern "C" int roma_refiner_assemble(const void* src, const float* flow, const float* weight, const float* bias, void* buf, int B, int C,
+                                     int E, int D, int pitch, int Hs, int Ws, int H, int W, int src_pitch, int src_batch_shift,
+                                     float gain, int dtype, void* stream) {
+  ROMA_REQUIRE(src && flow && weight && bias && buf, ROMA_E_ARG, "roma_refiner_assemble: null pointer");
+  ROMA_REQUIRE(B > 0 && C > 0 && E > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0 && D >= 2 * C + E && pitch >= D && src_pitch >= C,
+               ROMA_E_SHAPE, "roma_refiner_assemble: bad shape");
+  ROMA_REQUIRE((size_t)B * H * W < ((size_t)1 << 31) && (size_t)B * Hs * Ws < ((size_t)1 << 31), ROMA_E_SHAPE,
+               "roma_refiner_assemble: more than 2^31 pixels");
+  ROMA_REQUIRE(src_batch_shift >= 0 && src_batch_shift < B, ROMA_E_ARG, "roma_refiner_assemble: src_batch_shift %d outside [0, B)", src_batch_shift);
+  ROMA_REQUIRE(dtype == ROMA_F16 || dtype == ROMA_BF16, ROMA_E_DTYPE, "roma_refiner_assemble: fp16 / bf16 only (fp32 uses the separate kernels)");
+  ROMA_REQUIRE(pitch % 8 == 0 && src_pitch % 8 == 0 && aligned16(buf) && aligned16(src), ROMA_E_ALIGN,
+               "roma_refiner_assemble: pitches must be multiples of 8 and bases 16-byte aligned");
+  const bool small = C == 9 && E == 6 && D == 24 && pitch == 24 && src_pitch >= 16;
+  ROMA_REQUIRE(small || (C % 8 == 0 && E % 8 == 0), ROMA_E_UNSUPPORTED,
+               "roma_refiner_assemble: C=%d, E=%d, D=%d, pitch=%d (C and E multiples of 8, or the 9 + 9 + 6 = 24 pixel)", C, E, D, pitch);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  AsmParams p{src, flow, weight, bias, buf, B, C, E, D, pitch, Hs, Ws, H, W, src_pitch, src_batch_shift, gain};
+  const size_t px = (size_t)B * H * W;
+  if (small) {
+    if (dtype == ROMA_F16) hipLaunchKernelGGL((assemble_9_6_kernel<half_t>), dim3(grid_for(px)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((assemble_9_6_kernel<bf16_t>), dim3(grid_for(px)), dim3(256), 0, s, p);
+  } else {
+    const size_t total = px * (size_t)(C / 8 + E / 8 + (pitch / 8 - D / 8));
+    if (dtype == ROMA_F16) hipLaunchKernelGGL((assemble_packets_kernel<half_t>), dim3(grid_for(total)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((assemble_packets_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, p);
+  }
   ROMA_CHECK_LAUNCH();
 }
 

@@ -76,9 +76,32 @@ def block_impl(Dp, dtype, B, h, w):
     return "split_small" if Dp <= 32 else "split_gemm"
 
 
+def project_impl(dtype, channels_last, K, N, out_pitch):
+    """Which implementation runs a Decoder.project call: "skinny" (ops.project_skinny, a streaming kernel) for the two finest scales'
+    (K, N) on dense channels-last 16-bit feature maps — what the encoder delivers under MIOpen solver search — into rows of a pitch
+    the kernel can store 16-byte packets to; "gemm" (torch.baddbmm) for everything else: fp32, planar maps, scales 4, 8 and 16."""
+    half = dtype in (torch.float16, torch.bfloat16)
+    if half and channels_last and (K, N) in ((64, 9), (128, 64)) and out_pitch % 8 == 0:
+        return "skinny"
+    return "gemm"
+
+
+def assemble_impl(dtype, y_channels_last, y_pitch, C, E, D, Dp):
+    """How a ConvRefiner's warp / displacement embedding / padding slices are written: "fused" (ops.refiner_assemble, one launch) for
+    16-bit buffers and a channels-last y of a pitch with whole packets, at whole-packet C and E or the scale-1 pixel (9 + 9 + 6 = 24);
+    "split" (ops.warp_bilinear, ops.disp_emb, zero_()) for fp32 and any other y."""
+    half = dtype in (torch.float16, torch.bfloat16)
+    if not (half and y_channels_last and y_pitch % 8 == 0):
+        return "split"
+    if C % 8 == 0 and E % 8 == 0:
+        return "fused"
+    return "fused" if (C, E, D, Dp) == (9, 6, 24, 24) and y_pitch >= 16 else "split"
+
+
 class ConvRefiner(nn.Module):
     """x, warped y, displacement embedding and local correlation are assembled in ONE channels-last buffer (pitch Dp: D padded to
-    8 channels, to 64 above 160): the decoder's projection GEMM writes x there, three kernels write the other channel slices.  A
+    8 channels, to 64 above 160): the decoder's projection writes x there, ops.refiner_assemble writes the warp, the embedding and the
+    padding (fp32: three separate calls, assemble_impl), ops.local_correlation its slice.  A
     block (depthwise 5x5 + BN + ReLU + 1x1) is run by the first row that applies (block_impl):
         fp16, Dp == 576, B*ceil(h/8)*ceil(w/16) >= 512   wide         ops.refiner_block_wide, one kernel
         fp16/bf16, Dp <= 32                              fused        ops.refiner_block (kpad 32), one kernel
@@ -169,11 +192,16 @@ class ConvRefiner(nn.Module):
             assert x.data_ptr() == buf.data_ptr() and x.stride(1) == 1, "x must already be channels [0, C) of buf"
         else:
             d[:, :C].copy_(x)
-        if Dp > D:
-            buf[..., D:].zero_()
         yy = y.to(dtype)
-        ops.warp_bilinear(yy, flow, out=d[:, C:2 * C], batch_shift=batch_shift)               # matcher.py:109
-        ops.disp_emb(flow, P.we, P.be, 40 / 32 * scale_factor, out=d[:, 2 * C:2 * C + E])      # :111-120
+        y_layout, y_pitch, yy = ops.feat_layout(yy)
+        y_ok = y_layout == ops.ROMA_NHWC and yy.data_ptr() % 16 == 0
+        if assemble_impl(dtype, y_ok, y_pitch, C, E, D, Dp) == "fused":
+            ops.refiner_assemble(buf, yy, flow, P.we, P.be, 40 / 32 * scale_factor, C, D, batch_shift=batch_shift)   # matcher.py:109-120
+        else:
+            if Dp > D:
+                buf[..., D:].zero_()
+            ops.warp_bilinear(yy, flow, out=d[:, C:2 * C], batch_shift=batch_shift)           # matcher.py:109
+            ops.disp_emb(flow, P.we, P.be, 40 / 32 * scale_factor, out=d[:, 2 * C:2 * C + E])  # :111-120
         if r:
             ops.local_correlation(d[:, :C], yy, r, flow=flow, out=d[:, 2 * C + E:D], batch_shift=batch_shift)   # :121-125
         impl = block_impl(Dp, dtype, B, h, w)
@@ -373,26 +401,37 @@ class Decoder(nn.Module):
             out[s] = (wt, b)
             if wt.shape[1] < 16:
                 out[s + "/16"] = (F.pad(wt, (0, 16 - wt.shape[1])).contiguous(), F.pad(b, (0, 16 - b.shape[0])).contiguous())
+            if project_impl(dtype, True, *wt.shape, 8) == "skinny":
+                out[s + "/skinny"] = ops.project_skinny_pack(wt, b)
         self._proj = (key, out)
         return out
 
     def project(self, s, f, dtype, out=None):
-        """1x1 conv + BN(eval) as one batched GEMM — matcher.py:366-371.  The NCHW feature map is the GEMM's transposed
-        operand (no layout copy) and the result lands channels-last, directly in `out` when given (a (B,h,w,C) slice of the
-        refiner's concat buffer).  Returns the (B,C,h,w) channels-last view."""
-        wt, b = self.folded_proj(dtype)[s]
+        """1x1 conv + BN(eval) — matcher.py:366-371.  The result lands channels-last, directly in `out` when given (a (B,h,w,C)
+        slice of the refiner's concat buffer).  Dense channels-last 16-bit maps of the two finest scales stream through
+        ops.project_skinny (project_impl); everything else is one batched GEMM whose transposed operand is the NCHW feature map (no
+        layout copy).  Returns the (B,C,h,w) channels-last view."""
+        proj = self.folded_proj(dtype)
+        wt, b = proj[s]
         B, C, h, w = f.shape
-        a = f.to(dtype).flatten(2).transpose(1, 2)                                            # (B, hw, Cin) view
+        f = f.to(dtype)
         n = wt.shape[1]
+        dense_nhwc = f.stride() == (h * w * C, 1, w * C, C) and f.data_ptr() % 16 == 0
         if out is None:
-            out = torch.empty((B, h, w, n), dtype=dtype, device=f.device)
+            pitch = (n + 15) // 16 * 16 if project_impl(dtype, dense_nhwc, C, n, 8) == "skinny" else n
+            out = torch.empty((B, h, w, pitch), dtype=dtype, device=f.device)[..., :n]
+        out_rows = out.stride() == (h * w * out.stride(2), w * out.stride(2), out.stride(2), 1) and out.data_ptr() % 16 == 0
+        if project_impl(dtype, dense_nhwc and out_rows, C, n, out.stride(2)) == "skinny":
+            ops.project_skinny(f.permute(0, 2, 3, 1).reshape(B * h * w, C), *proj[s + "/skinny"], n,
+                               out.as_strided((B * h * w, n), (out.stride(2), 1)))
+            return out.permute(0, 3, 1, 2)
         tgt = out
         if n < 16 and out.stride(2) >= 16 and out.storage_offset() == 0:
             # the 64 -> 9 projection of scale 1: hipBLASLt runs N = 16 25 % faster than N = 9; the 7 extra (zero) columns
             # land in channels the warp / embedding kernels overwrite afterwards
             tgt = out.as_strided((B, h, w, 16), out.stride())
-            wt, b = self.folded_proj(dtype)[s + "/16"]
-        torch.baddbmm(b, a, wt.unsqueeze(0).expand(B, -1, -1), out=tgt.view(B, h * w, tgt.shape[-1]))
+            wt, b = proj[s + "/16"]
+        torch.baddbmm(b, f.flatten(2).transpose(1, 2), wt.unsqueeze(0).expand(B, -1, -1), out=tgt.view(B, h * w, tgt.shape[-1]))
         return out.permute(0, 3, 1, 2)
 
     @torch.no_grad()
@@ -411,8 +450,7 @@ class Decoder(nn.Module):
             flow = pixel_grid(b, *sizes[first], device)                                      # :346
             certainty = None                                                                 # the reference's 0.0
         else:
-            flow = ops.interp_bilinear(flow, sizes[first])                                   # :349-360
-            certainty = ops.interp_bilinear(certainty, sizes[first])
+            flow, certainty = ops.interp_bilinear_pair(flow, certainty, sizes[first])         # :349-360
         corresps = {}
         for s in all_scales:
             ins = int(s)
@@ -463,8 +501,7 @@ class Decoder(nn.Module):
                 batch_shift=shift)
             corresps[ins].update({"certainty": certainty, "flow": flow})
             if s != "1":
-                flow = ops.interp_bilinear(flow, sizes[ins // 2])                             # :408-417
-                certainty = ops.interp_bilinear(certainty, sizes[ins // 2])
+                flow, certainty = ops.interp_bilinear_pair(flow, certainty, sizes[ins // 2])   # :408-417
         return corresps
 
 

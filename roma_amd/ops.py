@@ -214,6 +214,46 @@ def interp_bilinear(x, size):
     return y
 
 
+def interp_bilinear_pair(a, b, size):
+    """(interp_bilinear(a, size), interp_bilinear(b, size)) for two fp32 maps of one size (the decoder's flow and certainty between
+    levels, matcher.py:408-417) in one launch; the same bits."""
+    _need_gpu(a, b)
+    B, Ca, Hi, Wi = a.shape
+    Bb, Cb = b.shape[:2]
+    if tuple(b.shape[2:]) != (Hi, Wi):
+        raise ValueError(f"the two maps differ in size: {tuple(a.shape)} and {tuple(b.shape)}")
+    Ho, Wo = int(size[0]), int(size[1])
+    a = a.float().contiguous()
+    b = b.float().contiguous()
+    ya = torch.empty((B, Ca, Ho, Wo), dtype=torch.float32, device=a.device)
+    yb = torch.empty((Bb, Cb, Ho, Wo), dtype=torch.float32, device=a.device)
+    check(_lib.load().roma_interp_bilinear_pair(_p(a), _p(ya), B * Ca, _p(b), _p(yb), Bb * Cb, Hi, Wi, Ho, Wo, _stream()),
+          "roma_interp_bilinear_pair")
+    return ya, yb
+
+
+def refiner_assemble(buf, src, flow, weight, bias, gain, C, D, batch_shift=0):
+    """The ConvRefiner's input assembly (matcher.py:109-120) in one launch, for a 16-bit channels-last concat buffer `buf` (B,h,w,Dp):
+    buf[..., C:2C] = warp_bilinear(src, flow, batch_shift), buf[..., 2C:2C+E] = disp_emb(flow, weight, bias, gain), buf[..., D:] = 0,
+    each element with the bits of those ops.  src: a (B,C,hs,ws) channels-last map, possibly channels [0, C) of buf itself.  Channels
+    [0, C) are not touched; of [2C+E, D) only what shares a 16-byte packet with channel D (zeroed) — local_correlation fills that
+    slice afterwards."""
+    _need_gpu(buf, src, flow, weight, bias)
+    B, H, W, Dp = buf.shape
+    E = weight.shape[0]
+    ls, ps, s = feat_layout(src)
+    if ls != ROMA_NHWC or s is not src or src.dtype != buf.dtype or not buf.is_contiguous():
+        raise ValueError("refiner_assemble: buf must be contiguous (B,h,w,Dp), src channels-last and of buf's dtype")
+    if tuple(flow.shape) != (B, 2, H, W) or src.shape[0] != B or src.shape[1] != C:
+        raise ValueError(f"refiner_assemble: flow {tuple(flow.shape)} / src {tuple(src.shape)} do not match buf {tuple(buf.shape)}, C = {C}")
+    flow = flow.float().contiguous()
+    w = weight.reshape(E, 2).float().contiguous()
+    bvec = bias.float().contiguous()
+    check(_lib.load().roma_refiner_assemble(_p(src), _p(flow), _p(w), _p(bvec), _p(buf), B, C, E, D, Dp, src.shape[2], src.shape[3], H, W,
+                                            ps, int(batch_shift) % B, float(gain), _dt(buf), _stream()), "roma_refiner_assemble")
+    return buf
+
+
 def flow_update(flow, certainty, delta, sx, sy):
     """In place: flow += (sx*delta[:,0], sy*delta[:,1]); returns (flow, certainty + delta[:,2:3]) — matcher.py:397-402.
     `certainty` may be None (the reference's 0.0 at the coarsest scale)."""
@@ -589,6 +629,34 @@ def pointwise_mfma(rows, wt, bias, C, out=None):
     assert out.shape == rows.shape and out.is_contiguous()
     check(_lib.load().roma_pointwise_mfma(_p(rows), _p(wt), _p(bias), _p(out), M, C, kpad, _dt(rows), pitch, pitch, _stream()),
           "roma_pointwise_mfma")
+    return out
+
+
+def project_skinny_pack(wt_in_out, bias):
+    """The weight layout of project_skinny from a (K, N) [in][out] 16-bit weight and its (N) bias: ((N padded to 16, K) [out][in] in
+    the weight's dtype, (N padded to 16) fp32 bias)."""
+    K, N = wt_in_out.shape
+    Np = (N + 15) // 16 * 16
+    wt = torch.zeros((Np, K), dtype=wt_in_out.dtype, device=wt_in_out.device)
+    wt[:N] = wt_in_out.t()
+    b = torch.zeros(Np, dtype=torch.float32, device=wt_in_out.device)
+    b[:N] = bias.float()
+    return wt, b
+
+
+def project_skinny(rows, wt, bias, N, out):
+    """out[p, 0:N] = bias + rows[p] @ wt[:N].T on the matrix cores, fp32 accumulation — the decoder's 64 -> 9 and 128 -> 64 projections
+    (matcher.py:366-371).  rows: (M, K) channels-last pixels, 16-bit, row pitch rows.stride(0); wt, bias from project_skinny_pack;
+    out: (M, >= N) rows of the same dtype with pitch out.stride(0) (a slice of the refiner's concat buffer): only columns [0, N) are
+    written."""
+    _need_gpu(rows, wt, bias, out)
+    M, K = rows.shape
+    if rows.stride(1) != 1 or out.stride(1) != 1 or out.shape[0] != M or out.shape[1] < N or out.dtype != rows.dtype or wt.dtype != rows.dtype:
+        raise ValueError("project_skinny: rows (M,K) and out (M,>=N) must be unit-stride rows of one 16-bit dtype")
+    if not wt.is_contiguous() or wt.shape[1] != K or wt.shape[0] < N or bias.dtype != torch.float32 or bias.numel() != wt.shape[0]:
+        raise ValueError("project_skinny: wt / bias are not what project_skinny_pack returns for these rows")
+    check(_lib.load().roma_project_skinny(_p(rows), _p(wt), _p(bias), _p(out), M, K, N, _dt(rows), rows.stride(0), out.stride(0), _stream()),
+          "roma_project_skinny")
     return out
 
 
