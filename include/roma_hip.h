@@ -415,6 +415,22 @@ int roma_refine_fundamental(const double* xa, const double* xb, const double* F_
                             double threshold, int iters, double* F, unsigned char* mask, double* cost, int* count, int* steps,
                             void* stream);
 
+/* Non-linear refinement of a homography (csrc/homography_refine.hip) — the polish cv2.findHomography(..., RANSAC)
+ * runs on the inliers after consensus, behind roma_ransac_select(kind 1).  xa, xb: (P,N,2) fp64 pixels, 16-byte aligned; H_in:
+ * (P,3,3), the model to start from (x_B ~ H x_A), any scale; mask_in: (P,N) uint8, the matches that may carry weight (NULL = all).
+ * Minimises the sum over the usable matches of min(e, threshold^2), e the squared forward transfer error in the pixels of image B
+ * (threshold in pixels, fp64), by at most `iters` damped Gauss-Newton steps over 8 entries of H^ = T_B H T_A^-1 in Hartley-normalised
+ * coordinates (the normalisation is computed in the kernel), scaled to unit Frobenius norm with its largest-magnitude entry held.  A
+ * step is kept only if it lowers the cost.
+ * H: (P,3,3), per pair EITHER a model with H[2,2] = 1 (unit Frobenius norm where |H[2,2]| < 1e-12 |H|) of strictly lower cost than
+ * H_in (steps >= 1), OR H_in bit for bit (steps = 0): no step lowered the cost, fewer than 4 weighted matches under H_in, a singular
+ * normal matrix, an H_in that is not finite or is all zero.  mask: (P,N) uint8, e < threshold^2 under the returned model; cost: (P)
+ * fp64 its cost; count: (P) int32 its inliers (= the sum of mask); steps: (P) int32 the steps kept.  Outputs must not overlap
+ * inputs.  One launch, no workspace, no host synchronisation; bitwise reproducible, and independent of the other pairs. */
+int roma_refine_homography(const double* xa, const double* xb, const double* H_in, const unsigned char* mask_in, int P, int N,
+                           double threshold, int iters, double* H, unsigned char* mask, double* cost, int* count, int* steps,
+                           void* stream);
+
 /* Two-view triangulation of matches under a known relative pose (csrc/triangulate.hip) — what a caller does with
  * the (R, t) of roma_recover_pose / roma_refine_pose: a point cloud of the sampled matches, or a depth map per image from every row of
  * the dense warp.  Convention of roma_recover_pose: x_B ~ K_B (R X_A + t).  Points are expressed in camera A's frame, in units of

@@ -90,6 +90,8 @@ SIGNATURES = {
                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "roma_refine_fundamental": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p],
+    "roma_refine_homography": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p],
     "roma_triangulate": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float,
                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }

@@ -36,7 +36,7 @@
 //               its own mask, cost and count, and steps = 0
 //
 // Shared with pose_refine.hip, in twoview_math.h: the residual, Match, block_sum, solve_step and the checks of the entry point; with
-// geometry.hip's select_kernel: Norm, to_pixels, jacobi_lds.  The schedules stay apart: here a candidate gets a cost pass, and
+// homography_refine.hip: load_pixels and the normalisation; with geometry.hip's select_kernel: Norm, to_pixels, jacobi_lds.  The schedules stay apart: here a candidate gets a cost pass, and
 // only a kept step a Jacobian pass.  The row of the normal equations and the mask loop are written out here as in pose_refine.hip:
 // this kernel sits at 256 VGPRs, and behind a shared function the compiler allocates its registers differently.
 #include "twoview_math.h"
@@ -49,46 +49,6 @@ constexpr int RF_NPAR = 7, RF_NTRI = 28, RF_NSUM = 37;          // 28 + 7 + cost
 constexpr int RF_COST = 35, RF_COUNT = 36;
 constexpr int RF_MIN_MATCHES = 8;
 constexpr double RF_LAMBDA0 = 1e-3, RF_LAMBDA_MIN = 1e-10, RF_ACCEPT_REL = 1e-12, RF_RANK_TOL = 1e-14;
-
-// match q in pixels; ok: finite and allowed by mask_in
-__device__ __forceinline__ Match load_pixels(const double2* __restrict__ xa, const double2* __restrict__ xb,
-                                             const unsigned char* mask_in, size_t q) {
-  const double2 a = xa[q], b = xb[q];
-  Match m;
-  m.x = a.x; m.y = a.y; m.u = b.x; m.v = b.y;
-  m.ok = isfinite(a.x) && isfinite(a.y) && isfinite(b.x) && isfinite(b.y) && (!mask_in || mask_in[q] != 0);
-  return m;
-}
-
-// Hartley normalisation of both images over the usable matches (geometry.hip's normalize_kernel, with the mask)
-__device__ __forceinline__ Norm normalisation(const double2* __restrict__ xa, const double2* __restrict__ xb, const unsigned char* mask_in,
-                                              size_t base, int N, double (*red)[RF_NSUM]) {
-  double c[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < N; i += RF_THREADS) {
-    const Match m = load_pixels(xa, xb, mask_in, base + i);
-    if (m.ok) { c[0] += m.x; c[1] += m.y; c[2] += m.u; c[3] += m.v; c[4] += 1.0; }
-  }
-  block_sum<5, RF_WAVES>(c, red);
-  const double cnt = c[4], inv = cnt > 0.0 ? 1.0 / cnt : 0.0;
-  Norm n;
-  n.cxA = c[0] * inv; n.cyA = c[1] * inv; n.cxB = c[2] * inv; n.cyB = c[3] * inv;
-  double d[2] = {0.0, 0.0};
-  for (int i = threadIdx.x; i < N; i += RF_THREADS) {
-    const Match m = load_pixels(xa, xb, mask_in, base + i);
-    if (m.ok) {
-      const double ax = m.x - n.cxA, ay = m.y - n.cyA, bx = m.u - n.cxB, by = m.v - n.cyB;
-      d[0] += sqrt(ax * ax + ay * ay);
-      d[1] += sqrt(bx * bx + by * by);
-    }
-  }
-  block_sum<2, RF_WAVES>(d, red);
-  const double mdA = d[0] * inv, mdB = d[1] * inv;
-  n.sA = 1.4142135623730951 / mdA;
-  n.sB = 1.4142135623730951 / mdB;
-  if (!(mdA > 0.0) || !isfinite(n.sA)) n.sA = 1.0;
-  if (!(mdB > 0.0) || !isfinite(n.sB)) n.sB = 1.0;
-  return n;
-}
 
 // o = T_B^-T f T_A^-1: normalised coordinates from pixels
 __device__ __forceinline__ void to_normalised(const double* f, const Norm& n, double* o) {
@@ -264,7 +224,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_fundamental_kernel(const do
 #pragma unroll
   for (int i = 0; i < 9; ++i) { f0[i] = fin[i]; good = good && isfinite(f0[i]); }
 
-  const Norm nrm = normalisation(xa, xb, mask_in, base, N, red);
+  const Norm nrm = normalisation<RF_THREADS>(xa, xb, mask_in, base, N, red);
 
   // the start: F^ = U diag(sigma_1, sigma_2, ~0) V^T from the eigenvectors of F^^T F^
   double U[9], V[9], s = 0.0;

@@ -2,7 +2,8 @@
 // counter-hash of the sample draw, fp32 scoring of every slot (score_kernel / reduce_kernel, no atomics; MSAC, or MAGSAC++ by the
 // loss and weight tables of magsac_table.h), the block-wide re-score of the select kernels, the workspace layout and the argument
 // checks of the entry points.  geometry.hip's header pins the draw and the tolerances.  DESIGN.md §3.4.
-// The refinement kernels (pose_refine.hip, fundamental_refine.hip) score nothing and include twoview_math.h alone.
+// The refinement kernels (pose_refine.hip, fundamental_refine.hip, homography_refine.hip) score nothing and include twoview_math.h
+// alone.
 #pragma once
 #include "magsac_table.h"
 #include "twoview_math.h"

@@ -1,7 +1,8 @@
-// The fp64 device helpers of the two-view geometry kernels (geometry.hip, essential.hip, pose_refine.hip, fundamental_refine.hip):
-// small 3 x 3 algebra, the unrolled elimination, the LDS Jacobi, the Sampson residual written out in fused multiply-adds, the
-// series of exp([w]x), the de-normalisation (select_kernel, the F refinement), and what the two refinement kernels run alike: the
-// fixed-order block reduction, the damped Cholesky step and (host) the checks of their entry points.  No __global__ code and no
+// The fp64 device helpers of the two-view geometry kernels (geometry.hip, essential.hip, pose_refine.hip, fundamental_refine.hip,
+// homography_refine.hip): small 3 x 3 algebra, the unrolled elimination, the LDS Jacobi, the Sampson residual written out in fused
+// multiply-adds, the series of exp([w]x), the de-normalisation (select_kernel, the F refinement), and what the refinement kernels run
+// alike: the fixed-order block reduction, the damped Cholesky step, (F and H) the Hartley normalisation over the usable matches and
+// (host) the checks of their entry points.  No __global__ code and no
 // device data: what the RANSAC scoring needs beyond this is ransac_common.h.  DESIGN.md §3.4.
 // The floating-point expressions in here are pinned: operand order, the explicit __builtin_fma calls, the bracketing of the sums
 // and the order of the butterflies are what the numpy restatements under tests/ repeat bit for bit.
@@ -214,7 +215,7 @@ __device__ __forceinline__ int argmin_diag(const double* A, int n) {
   return j;
 }
 
-// ------------------------------------------------------------------ what the refinement kernels share (pose_refine, fundamental_refine)
+// ------------------------------------------- what the refinement kernels share (pose_refine, fundamental_refine, homography_refine)
 // one match in the coordinates of the residual; ok: finite and allowed by mask_in
 struct Match {
   double x, y, u, v;
@@ -244,6 +245,47 @@ template <int K, int WAVES, int LD> __device__ __forceinline__ void block_sum(do
     s[k] = acc;
   }
   __syncthreads();
+}
+
+// match q in pixels; ok: finite and allowed by mask_in (the refinements in pixels: fundamental_refine, homography_refine)
+__device__ __forceinline__ Match load_pixels(const double2* __restrict__ xa, const double2* __restrict__ xb,
+                                             const unsigned char* mask_in, size_t q) {
+  const double2 a = xa[q], b = xb[q];
+  Match m;
+  m.x = a.x; m.y = a.y; m.u = b.x; m.v = b.y;
+  m.ok = isfinite(a.x) && isfinite(a.y) && isfinite(b.x) && isfinite(b.y) && (!mask_in || mask_in[q] != 0);
+  return m;
+}
+
+// Hartley normalisation of both images over the usable matches (geometry.hip's normalize_kernel, with the mask)
+template <int THREADS, int LD>
+__device__ __forceinline__ Norm normalisation(const double2* __restrict__ xa, const double2* __restrict__ xb, const unsigned char* mask_in,
+                                              size_t base, int N, double (*red)[LD]) {
+  double c[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < N; i += THREADS) {
+    const Match m = load_pixels(xa, xb, mask_in, base + i);
+    if (m.ok) { c[0] += m.x; c[1] += m.y; c[2] += m.u; c[3] += m.v; c[4] += 1.0; }
+  }
+  block_sum<5, THREADS / 64>(c, red);
+  const double cnt = c[4], inv = cnt > 0.0 ? 1.0 / cnt : 0.0;
+  Norm n;
+  n.cxA = c[0] * inv; n.cyA = c[1] * inv; n.cxB = c[2] * inv; n.cyB = c[3] * inv;
+  double d[2] = {0.0, 0.0};
+  for (int i = threadIdx.x; i < N; i += THREADS) {
+    const Match m = load_pixels(xa, xb, mask_in, base + i);
+    if (m.ok) {
+      const double ax = m.x - n.cxA, ay = m.y - n.cyA, bx = m.u - n.cxB, by = m.v - n.cyB;
+      d[0] += sqrt(ax * ax + ay * ay);
+      d[1] += sqrt(bx * bx + by * by);
+    }
+  }
+  block_sum<2, THREADS / 64>(d, red);
+  const double mdA = d[0] * inv, mdB = d[1] * inv;
+  n.sA = 1.4142135623730951 / mdA;
+  n.sB = 1.4142135623730951 / mdB;
+  if (!(mdA > 0.0) || !isfinite(n.sA)) n.sA = 1.0;
+  if (!(mdB > 0.0) || !isfinite(n.sB)) n.sB = 1.0;
+  return n;
 }
 
 // delta of (A + lambda diag A) delta = -g by a Cholesky in registers; tri: the upper triangle of A row by row, g: J^T r.  False
@@ -293,7 +335,7 @@ template <int NPAR> __device__ __forceinline__ bool solve_step(const double* tri
   return ok;
 }
 
-// host: what the entry points of the two refinements check alike (fn names the entry point in the message)
+// host: what the entry points of the refinements check alike (fn names the entry point in the message)
 inline int check_refine(const char* fn, const void* xa, const void* xb, int P, int N, int min_matches, double threshold, int iters) {
   ROMA_REQUIRE(P >= 1 && P <= (1 << 24), ROMA_E_SHAPE, "%s: bad shape P=%d", fn, P);
   ROMA_REQUIRE(N >= min_matches && N <= (1 << 26), ROMA_E_SHAPE, "%s: N=%d matches, need at least %d", fn, N, min_matches);

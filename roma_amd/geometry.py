@@ -27,6 +27,11 @@ poselib.estimate_relative_pose, the call of the reference's PoseLib benchmark
 Sampson cost in pixels over the rank-2 manifold, what cv2.findFundamentalMat runs after consensus.  `find_fundamental` and
 `estimate_pose_uncalibrated` run it on request (refine_iters > 0).
 
+`refine_homography` is that polish for a homography (csrc/homography_refine.hip): Levenberg-Marquardt on the truncated forward
+transfer cost in the pixels of image B, what cv2.findHomography(..., cv2.RANSAC) runs on its inliers after consensus — the call of
+the reference's HPatches benchmark (hpatches_sequences_homog_benchmark.py:80-86).  `find_homography` runs it on request
+(refine_iters > 0), and `homography_corner_error` is that benchmark's metric (lines 92-103) on the device.
+
 `triangulate` turns matches and a relative pose into 3-D points, depths, reprojection errors and a validity flag per match
 (csrc/triangulate.hip: fp32 per match from pair constants prepared in fp64; Lindstrom's optimal correction or the midpoint), and
 `depth_from_warp` does so for every row of the dense warp of match() in one launch: a depth map per image.
@@ -195,9 +200,13 @@ def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_
 
 
 def _refine_iters(refine_iters):
-    if int(refine_iters) < 0:
+    try:
+        n = int(refine_iters)
+    except (TypeError, ValueError):                     # e.g. a scoring name passed by position: scoring is keyword-only
+        raise TypeError(f"refine_iters must be an integer, got {refine_iters!r}") from None
+    if n < 0:
         raise ValueError(f"refine_iters must be >= 0, got {refine_iters}")
-    return int(refine_iters)
+    return n
 
 
 def find_fundamental(x_A, x_B, threshold=3.0, max_iters=10000, seed=None, lo_iters=3, refine_iters=0, *, scoring="msac"):
@@ -215,10 +224,18 @@ def find_fundamental(x_A, x_B, threshold=3.0, max_iters=10000, seed=None, lo_ite
     return refine_fundamental(F, x_A, x_B, threshold, refine_iters)
 
 
-def find_homography(x_A, x_B, threshold=3.0, max_iters=2000, seed=None, lo_iters=3, *, scoring="msac"):
+def find_homography(x_A, x_B, threshold=3.0, max_iters=2000, seed=None, lo_iters=3, refine_iters=0, *, scoring="msac"):
     """Homography H (x_B ~ H x_A) of pixel correspondences, shapes as find_fundamental.  Returns (H fp64 with H[2,2] = 1 — unit
-    Frobenius norm if |H[2,2]| < 1e-12 |H| —, inlier mask: forward transfer error below threshold).  scoring: "msac" or "magsac"."""
-    return _estimate(x_A, x_B, KIND_H, threshold, max_iters, seed, lo_iters, scoring=scoring)
+    Frobenius norm if |H[2,2]| < 1e-12 |H| —, inlier mask: forward transfer error below threshold).  refine_iters > 0 polishes the
+    RANSAC model by refine_homography on all matches at the same threshold (at most that many Levenberg-Marquardt steps) and returns
+    the refined model's mask; 0, the default, returns the RANSAC model as it is.  scoring: "msac" or "magsac"; the refinement keeps
+    its truncated transfer cost either way."""
+    _scoring(scoring)
+    refine_iters = _refine_iters(refine_iters)
+    H, mask = _estimate(x_A, x_B, KIND_H, threshold, max_iters, seed, lo_iters, scoring=scoring)
+    if refine_iters == 0:
+        return H, mask
+    return refine_homography(H, x_A, x_B, threshold, refine_iters)
 
 
 def find_essential(x_A, x_B, K_A, K_B, threshold, max_iters=2000, seed=None, lo_iters=3, *, scoring="msac"):
@@ -344,6 +361,43 @@ def refine_pose(R, t, x_A, x_B, K_A, K_B, threshold, iters=15, mask=None, return
     return res + ({k: v[0] for k, v in info.items()} if single else info,)
 
 
+def _refine_model(M, x_A, x_B, kind, least, entry, threshold, iters, mask, return_info):
+    """what refine_fundamental and refine_homography run alike: the checks, the outputs and the call of the C entry point `entry`"""
+    name = "F" if kind == KIND_F else "H"
+    _need_gpu(M)
+    if not float(threshold) > 0:
+        raise ValueError(f"threshold must be positive, got {threshold}")
+    if int(iters) < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    xa, xb, single = _points(x_A, x_B, kind)
+    P, N = xa.shape[0], xa.shape[1]
+    if N < least:
+        raise ValueError(f"{N} matches, the refinement needs {least}")
+    if M.shape != ((3, 3) if single else (P, 3, 3)):
+        raise ValueError(f"{name} {tuple(M.shape)} does not match the points {tuple(x_A.shape)}")
+    m0 = M.reshape(P, 3, 3).to(torch.float64).contiguous()
+    m = None
+    if mask is not None:
+        _need_gpu(mask)
+        if mask.shape != ((N,) if single else (P, N)):
+            raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
+        m = mask.reshape(P, N).to(torch.uint8).contiguous()
+    Mo = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
+    out = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
+    cost = torch.empty((P,), dtype=torch.float64, device=xa.device)
+    count = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    steps = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    check(getattr(_lib.load(), entry)(xa.data_ptr(), xb.data_ptr(), m0.data_ptr(), None if m is None else m.data_ptr(), P, N,
+                                      float(threshold), int(iters), Mo.data_ptr(), out.data_ptr(), cost.data_ptr(), count.data_ptr(),
+                                      steps.data_ptr(), _stream()), entry)
+    out = out.bool()
+    res = (Mo[0], out[0]) if single else (Mo, out)
+    if not return_info:
+        return res
+    info = {"cost": cost, "count": count, "steps": steps}
+    return res + ({k: v[0] for k, v in info.items()} if single else info,)
+
+
 def refine_fundamental(F, x_A, x_B, threshold=3.0, iters=15, mask=None, return_info=False):
     """Non-linear refinement of a fundamental matrix F — of find_fundamental — on the matches it was estimated from: Levenberg-
     Marquardt, at most `iters` steps, on the sum over the matches of min(r^2, threshold^2), r the Sampson residual in pixels (what
@@ -354,38 +408,34 @@ def refine_fundamental(F, x_A, x_B, threshold=3.0, iters=15, mask=None, return_i
     steps kept).  A pair comes back either as a rank-2 model of unit Frobenius norm, largest-magnitude entry positive, of strictly
     lower cost than the given F, or — no step lowered the cost, fewer than 8 weighted matches, a singular normal matrix, an F that is
     not finite or has rank below 2 — as the given F bit for bit, with steps = 0."""
-    _need_gpu(F)
-    if not float(threshold) > 0:
-        raise ValueError(f"threshold must be positive, got {threshold}")
-    if int(iters) < 0:
-        raise ValueError(f"iters must be >= 0, got {iters}")
-    xa, xb, single = _points(x_A, x_B, KIND_F)
-    P, N = xa.shape[0], xa.shape[1]
-    if N < 8:
-        raise ValueError(f"{N} matches, the refinement needs 8")
-    if F.shape != ((3, 3) if single else (P, 3, 3)):
-        raise ValueError(f"F {tuple(F.shape)} does not match the points {tuple(x_A.shape)}")
-    f0 = F.reshape(P, 3, 3).to(torch.float64).contiguous()
-    m = None
-    if mask is not None:
-        _need_gpu(mask)
-        if mask.shape != ((N,) if single else (P, N)):
-            raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
-        m = mask.reshape(P, N).to(torch.uint8).contiguous()
-    Fo = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
-    out = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
-    cost = torch.empty((P,), dtype=torch.float64, device=xa.device)
-    count = torch.empty((P,), dtype=torch.int32, device=xa.device)
-    steps = torch.empty((P,), dtype=torch.int32, device=xa.device)
-    check(_lib.load().roma_refine_fundamental(xa.data_ptr(), xb.data_ptr(), f0.data_ptr(), None if m is None else m.data_ptr(), P, N,
-                                              float(threshold), int(iters), Fo.data_ptr(), out.data_ptr(), cost.data_ptr(),
-                                              count.data_ptr(), steps.data_ptr(), _stream()), "roma_refine_fundamental")
-    out = out.bool()
-    res = (Fo[0], out[0]) if single else (Fo, out)
-    if not return_info:
-        return res
-    info = {"cost": cost, "count": count, "steps": steps}
-    return res + ({k: v[0] for k, v in info.items()} if single else info,)
+    return _refine_model(F, x_A, x_B, KIND_F, 8, "roma_refine_fundamental", threshold, iters, mask, return_info)
+
+
+def refine_homography(H, x_A, x_B, threshold=3.0, iters=15, mask=None, return_info=False):
+    """Non-linear refinement of a homography H — of find_homography — on the matches it was estimated from: Levenberg-Marquardt, at
+    most `iters` steps, on the sum over the matches of min(e, threshold^2), e the squared forward transfer error in the pixels of
+    image B (what find_homography scores with), over 8 entries of the Hartley-normalised H with its largest entry held.  Matches
+    beyond the threshold carry no weight, and `mask` (bool / uint8) optionally names the only matches that may carry any.  H (3,3)
+    or (P,3,3); points as find_homography.  Returns (H fp64, mask bool: e < threshold^2 under the returned model); with return_info
+    also a dict of device tensors: cost (fp64, the truncated cost of the returned model), count (int32, its inliers), steps (int32,
+    the steps kept).  A pair comes back either as a model with H[2,2] = 1 (find_homography's convention) of strictly lower cost than
+    the given H, or — no step lowered the cost, fewer than 4 weighted matches, a singular normal matrix, an H that is not finite or
+    is all zero — as the given H bit for bit, with steps = 0."""
+    return _refine_model(H, x_A, x_B, KIND_H, 4, "roma_refine_homography", threshold, iters, mask, return_info)
+
+
+def homography_corner_error(H, H_gt, w, h, scale=1.0):
+    """The metric of the reference's HPatches benchmark (hpatches_sequences_homog_benchmark.py:92-103) in torch on the device,
+    batched: the mean distance in pixels between the corners (0,0), (0,h-1), (w-1,0), (w-1,h-1) of image A warped by H and by H_gt,
+    divided by `scale` (the benchmark passes min(w2, h2) / 480).  H, H_gt (...,3,3), H_gt a tensor or numpy; fp64.  An all-zero H —
+    find_homography's "no model" — gives inf."""
+    _need_gpu(H)
+    H = H.to(torch.float64)
+    H_gt = torch.as_tensor(H_gt).to(device=H.device, dtype=torch.float64)
+    c = torch.tensor([[0, 0, 1], [0, h - 1, 1], [w - 1, 0, 1], [w - 1, h - 1, 1]], dtype=torch.float64).to(H.device)
+    a, b = c @ H.transpose(-1, -2), c @ H_gt.transpose(-1, -2)
+    d = torch.linalg.norm(a[..., :2] / a[..., 2:] - b[..., :2] / b[..., 2:], dim=-1).mean(-1) / scale
+    return torch.where(torch.isnan(d) & ~H.any(-1).any(-1), torch.full_like(d, float("inf")), d)
 
 
 class RelativePose:

@@ -6,6 +6,8 @@
 # recover_pose + refine_pose), at the two pose shapes; their lines give the kept steps instead of model-point evaluations.
 # refineF = refine_fundamental alone from the model of find_fundamental (seed 0), Fref = find_fundamental(refine_iters=15), at the
 # two F shapes: the extra cost of the refinement inside the estimator is Fref minus F of the same run.
+# refineH = refine_homography alone from the model of find_homography (seed 0), Href = find_homography(refine_iters=15), at the H
+# shape and at P = 64 / N = 5 000: the extra cost of the refinement inside the estimator is Href minus H of the same run.
 # `ransac_micro.py 10 F,H,E msac,magsac` adds the MAGSAC++ scoring: every F / H / E / pose case is then timed with each scoring named,
 # at its threshold and at the generous one of DESIGN.md §3.4 (WIDE: where MAGSAC++ is meant to be used, and where it looks up more
 # inliers), and the magsac lines end with their time over the msac time of the same case and threshold.
@@ -20,13 +22,16 @@ from roma_amd import geometry  # noqa: E402
 from tests import geometry_ref as G  # noqa: E402
 from tests import pose_ref as PR  # noqa: E402
 
-CASES = [("F", 1, 10000, 10000, 1.5), ("F", 64, 5000, 10000, 1.5), ("H", 1, 5000, 2000, 3.0),
+CASES = [("F", 1, 10000, 10000, 1.5), ("F", 64, 5000, 10000, 1.5), ("H", 1, 5000, 2000, 3.0), ("H", 64, 5000, 2000, 3.0),
          ("E", 1, 10000, 2000, 1.5 / 800), ("E", 64, 5000, 2000, 1.5 / 800), ("pose", 1, 10000, 2000, 1.5 / 800),
          ("pose", 64, 5000, 2000, 1.5 / 800), ("refine", 1, 10000, 2000, 1.5 / 800), ("refine", 64, 5000, 2000, 1.5 / 800),
          ("relpose", 1, 10000, 2000, 1.5 / 800), ("relpose", 64, 5000, 2000, 1.5 / 800),
-         ("refineF", 1, 10000, 10000, 1.5), ("refineF", 64, 5000, 10000, 1.5), ("Fref", 1, 10000, 10000, 1.5), ("Fref", 64, 5000, 10000, 1.5)]
-MODEL = {"F": "fundamental", "H": "homography", "E": "essential", "pose": "essential", "Fref": "fundamental"}
+         ("refineF", 1, 10000, 10000, 1.5), ("refineF", 64, 5000, 10000, 1.5), ("Fref", 1, 10000, 10000, 1.5), ("Fref", 64, 5000, 10000, 1.5),
+         ("refineH", 1, 5000, 2000, 3.0), ("refineH", 64, 5000, 2000, 3.0), ("Href", 1, 5000, 2000, 3.0), ("Href", 64, 5000, 2000, 3.0)]
+MODEL = {"F": "fundamental", "H": "homography", "E": "essential", "pose": "essential", "Fref": "fundamental",
+         "Href": "homography"}
 CAMERA = {"model": "PINHOLE", "params": [800.0, 800.0, G.W_IMG / 2, G.H_IMG / 2]}
+PLANAR = ("H", "refineH", "Href")
 WIDE = {"F": 6.0, "H": 25.0, "E": 6.0 / 800, "pose": 6.0 / 800}
 
 
@@ -34,21 +39,21 @@ _SCENES = {}
 
 
 def scene(kind, P, N):
-    key = (kind == "H", P, N)
+    key = (kind in PLANAR, P, N)
     if key not in _SCENES:
         _SCENES[key] = _scene(kind, P, N)
     return _SCENES[key]
 
 
 def _scene(kind, P, N):
-    make = G.planar_scene if kind == "H" else G.two_view_scene
+    make = G.planar_scene if kind in PLANAR else G.two_view_scene
     pts = [make(100 + i, N=N)[:2] for i in range(P)]
     return (torch.from_numpy(np.stack([p[0] for p in pts])).float().cuda(), torch.from_numpy(np.stack([p[1] for p in pts])).float().cuda())
 
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-    kinds = sys.argv[2].split(",") if len(sys.argv) > 2 else ["F", "H", "E", "pose", "refine", "relpose", "refineF", "Fref"]
+    kinds = sys.argv[2].split(",") if len(sys.argv) > 2 else ["F", "H", "E", "pose", "refine", "relpose", "refineF", "Fref", "refineH", "Href"]
     scorings = sys.argv[3].split(",") if len(sys.argv) > 3 else ["msac"]
     K = torch.from_numpy(PR.K_SCENE).cuda()
     runs = [(c, "msac", c[4]) for c in CASES]
@@ -85,6 +90,14 @@ def main():
         elif kind == "Fref":
             def fn(a, b, threshold, max_iters, seed):
                 return geometry.find_fundamental(a, b, threshold=threshold, max_iters=max_iters, seed=seed, refine_iters=15)
+        elif kind == "refineH":
+            H0, _ = geometry.find_homography(xa, xb, threshold=thr, max_iters=iters, seed=0)
+
+            def fn(a, b, threshold, max_iters, seed):
+                return geometry.refine_homography(H0, a, b, threshold, return_info=True)
+        elif kind == "Href":
+            def fn(a, b, threshold, max_iters, seed):
+                return geometry.find_homography(a, b, threshold=threshold, max_iters=max_iters, seed=seed, refine_iters=15)
         else:
             def fn(a, b, threshold, max_iters, seed):
                 return (geometry.find_fundamental if kind == "F" else geometry.find_homography)(a, b, threshold=threshold,
@@ -101,7 +114,7 @@ def main():
             torch.cuda.synchronize()
             times.append(s.elapsed_time(e))
         ms = float(np.median(times))
-        if kind in ("refine", "relpose", "refineF"):
+        if kind in ("refine", "relpose", "refineF", "refineH"):
             out = fn(xa, xb, threshold=thr, max_iters=iters, seed=0)
             steps = (out[1]["refinements"] if kind == "relpose" else out[-1]["steps"]).float()
             print(f"{kind:7s} P={P:3d} N={N:5d} iters={iters:5d}: {ms:8.3f} ms/call (median of {reps}, min {min(times):.3f})  "
