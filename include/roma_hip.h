@@ -458,6 +458,53 @@ int roma_triangulate(const float* m, const float* to_px, const double* Ka, const
                      const unsigned char* mask_in, int P, int N, int method, float max_reproj, float max_cos_parallax, float* points,
                      float* depth_a, float* depth_b, float* reproj, float* cos_parallax, unsigned char* valid, void* stream);
 
+/* Ground-truth warp of key-points from two depth maps and a relative pose (csrc/depth_warp.hip): warp_kpts of the
+ * reference (romatch/utils/utils.py:358-455; get_gt_warp is this on the pixel grid).  Convention: X_B = R X_A + t, T = [R | t].
+ *   x: (P,N,·) fp32 device, 8-byte aligned, normalised key-points of image A in columns 0-1 of rows `x_stride` floats apart: 2 for
+ *     packed (P,N,2), 4 to read the first two columns of a (P,N,4) warp; any other stride returns ROMA_E_ARG;
+ *   depth_a: (P,Ha,Wa), depth_b: (P,Hb,Wb) fp32, contiguous, 0 = no depth; sides 1 to 32768;
+ *   T: (P,3,4) fp64 row major; Ka, Kb: (P,3,3) fp64, any 3x3 (Ka is inverted by its adjugate);
+ *   mode: 0 = bilinear, 1 = nearest, 2 = combined; threshold: on the relative depth error, not NaN.
+ * Per point, in fp64 from the fp32 inputs widened (the reference casts exactly these to double):
+ *   d = depth_a sampled at (x, y) as grid_sample does with align_corners=False and zero padding: ix = ((x + 1) Wa - 1) / 2; bilinear
+ *     taps outside the map contribute 0; nearest rounds ix, iy to the nearest integer, ties to even, and gives 0 outside the map;
+ *   (px, py) = (Wa (x + 1) / 2, Ha (y + 1) / 2);  X_A = Ka^-1 (px d, py d, d);  X_B = R X_A + t;  z = X_B.z;
+ *   (u, v) = (Kb X_B).xy / ((Kb X_B).z + 1e-4);  covisible = 0 < u < Wb - 1 and 0 < v < Hb - 1, all strict;
+ *   x2 = (2 u / Wb - 1, 2 v / Hb - 1);  d_B = depth_b sampled at x2 with the same sampler;  rel_err = |(d_B - z) / d_B|;
+ *   valid = d != 0 and covisible and rel_err < threshold.
+ * IEEE semantics only: a comparison with NaN is false, a zero d_B gives rel_err = inf (NaN when z = 0 too), and such a point is not
+ * valid.  A key-point that is NaN, inf or far outside samples 0 (the sampler range-checks in floating point before it forms an index)
+ * and is not valid; a singular Ka makes every point of its pair not valid.  mode 2 computes both samplers' results and returns the
+ * nearest one (x2 and rel_err) where the bilinear one is not valid and the nearest one is, the bilinear one elsewhere; valid is the OR.
+ * Outputs, device, each may be NULL but not all: x2 (P,N,2) fp64, 16-byte aligned, normalised in B; valid (P,N) uint8; rel_err (P,N)
+ * fp64.  Every requested element is written (x2 and rel_err may be inf / NaN where valid is 0); an output does not depend on which
+ * others are requested, nor a pair on the other pairs.  One launch, no workspace, no atomics, no host synchronisation. */
+int roma_warp_kpts(const float* x, int x_stride, const float* depth_a, const float* depth_b, const double* T, const double* Ka,
+                   const double* Kb, int P, int N, int Ha, int Wa, int Hb, int Wb, int mode, double threshold, double* x2,
+                   unsigned char* valid, double* rel_err, void* stream);
+
+/* End-point error and PCK of a dense warp against that ground truth, fused (csrc/depth_warp.hip): geometric_dist of the reference's
+ * MegadepthDenseBenchmark (romatch/benchmarks/megadepth_dense_benchmark.py:17-42).
+ *   warp: (P,H,W,4) fp32 device, 16-byte aligned, rows [x_A, y_A, predicted x_B, y_B] normalised; `pitch` is the distance in floats
+ *     between image rows (a multiple of 4, >= 4 W; else ROMA_E_ARG) and a pair is H * pitch floats: pitch = 8 W reads the left half
+ *     of a symmetric (P,H,2W,4) warp in place.  H, W: 1 to 32768, H * W <= 2^28;
+ *   depth_a, depth_b, T, Ka, Kb, Ha, Wa, Hb, Wb, mode, threshold: as roma_warp_kpts.
+ * Per pixel: (x2, valid) = the chain of roma_warp_kpts on columns 0-1; x2_px = (W (x2 + 1) / 2, H (y2 + 1) / 2) in fp64 with the W, H
+ * of the WARP (as the reference; not those of depth_b); xhat_px = ((W (c2 + 1)) / 2, (H (c3 + 1)) / 2) of columns 2-3 in fp32 in
+ * exactly this order (dense_matches is fp32 in the reference), then widened; gd = |xhat_px - x2_px| in fp64.
+ * Per pair: epe_sum (P) fp64 = the sum of gd over the valid pixels; counts (P,4) int64 = the number of valid pixels and of those with
+ * gd < 1, gd < 3, gd < 5, all strict.  The mean end-point error is epe_sum / counts[0], PCK@k counts[k] / counts[0]; over a batch,
+ * the sums of both.  A valid pixel whose prediction is NaN puts NaN into epe_sum and into no count, as the reference's mean would.
+ * Optional per-pixel outputs, NULL to skip: gd (P,H,W) fp64 (of every pixel; inf / NaN possible where valid is 0), valid (P,H,W) uint8.
+ *   workspace: device, 8-byte aligned, workspace_bytes >= P * ceil(H * W / 1024) * 40 (else ROMA_E_ARG): one 40-byte partial (fp64
+ *     sum, four int64 counts) per workgroup of 1024 pixels; need not be initialised.
+ * Two launches: the first leaves the partials (wave butterfly, the waves through LDS in order), the second adds each pair's in a
+ * fixed order.  No atomics, no host synchronisation; bitwise reproducible, and a pair does not depend on the other pairs. */
+int roma_dense_match_metrics(const float* warp, long pitch, const float* depth_a, const float* depth_b, const double* T,
+                             const double* Ka, const double* Kb, int P, int H, int W, int Ha, int Wa, int Hb, int Wb, int mode,
+                             double threshold, void* workspace, long workspace_bytes, double* epe_sum, long long* counts, double* gd,
+                             unsigned char* valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,10 @@ the reference's HPatches benchmark (hpatches_sequences_homog_benchmark.py:80-86)
 `triangulate` turns matches and a relative pose into 3-D points, depths, reprojection errors and a validity flag per match
 (csrc/triangulate.hip: fp32 per match from pair constants prepared in fp64; Lindstrom's optimal correction or the midpoint), and
 `depth_from_warp` does so for every row of the dense warp of match() in one launch: a depth map per image.
+
+`warp_kpts` and `get_gt_warp` are the reference's ground-truth warp from two depth maps and a relative pose (romatch/utils/utils.py:
+326-455; csrc/depth_warp.hip, fp64 per point as there), and `dense_match_metrics` / `geometric_dist` the dense MegaDepth benchmark's
+EPE and PCK@1/3/5 of a warp against it (romatch/benchmarks/megadepth_dense_benchmark.py:17-42), fused into one pass.
 """
 from __future__ import annotations
 
@@ -736,3 +740,175 @@ def depth_from_warp(warp, certainty, R, t, K_A, K_B, H_A, W_A, H_B=None, W_B=Non
     W = W2 // 2 if symmetric else W2
     res = (da[..., :W], valid[..., :W], db[..., W:] if symmetric else None, valid[..., W:] if symmetric else None, points, valid)
     return WarpDepth(*((None if o is None else o[0]) for o in res) if single else res)
+
+
+# ------------------------------------------------------------------------------------- ground-truth warp from depth, dense metrics
+_DEPTH_MODES = {"bilinear": 0, "nearest": 1, "combined": 2}
+_METRICS_PIXELS_PER_PARTIAL, _METRICS_PARTIAL_BYTES = 1024, 40
+
+
+def dense_metrics_workspace(P, H, W):
+    """Bytes of workspace roma_dense_match_metrics needs for P warps of H x W (include/roma_hip.h): one 40-byte partial per 1024
+    pixels of a pair."""
+    return P * (-(-(H * W) // _METRICS_PIXELS_PER_PARTIAL)) * _METRICS_PARTIAL_BYTES
+
+
+class DenseMatchMetrics:
+    """What dense_match_metrics returns, all device tensors.  Per pair (P,): epe_sum fp64 = the sum of the end-point error in pixels
+    over the pixels with a ground truth, n_valid, n_pck_1, n_pck_3, n_pck_5 int64 = their number and how many lie within 1, 3, 5 px.
+    Pooled over the batch (0-d fp64): epe, pck_1, pck_3, pck_5 = the sum of sums over the sum of counts (NaN when no pixel has a
+    ground truth), computed when read.  counts (P,4) int64 holds the four n_ columns.  With return_maps: gd (P,H,W) fp64 of every
+    pixel and prob (P,H,W) fp32, 1 where the ground truth is valid; else None."""
+    __slots__ = ("epe_sum", "counts", "gd", "prob")
+
+    def __init__(self, epe_sum, counts, gd, prob):
+        self.epe_sum, self.counts, self.gd, self.prob = epe_sum, counts, gd, prob
+
+    n_valid, n_pck_1, n_pck_3, n_pck_5 = (property(lambda self, k=k: self.counts[:, k]) for k in range(4))
+
+    def _pooled(self, k):
+        total = self.counts.sum(0).to(torch.float64)
+        return total[k] / total[0]
+
+    epe = property(lambda self: self.epe_sum.sum() / self.counts[:, 0].sum().to(torch.float64))
+    pck_1, pck_3, pck_5 = (property(lambda self, k=k: self._pooled(k)) for k in (1, 2, 3))
+
+    def __repr__(self):
+        return f"DenseMatchMetrics(pairs={self.epe_sum.shape[0]}, device={self.epe_sum.device})"
+
+
+def _depth_mode(mode, threshold):
+    """-> (mode code, threshold), checked before anything looks at a tensor"""
+    if mode not in _DEPTH_MODES:
+        raise ValueError(f"unknown depth_interpolation_mode {mode!r}: 'bilinear', 'nearest' or 'combined'")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("relative_depth_error_threshold must not be NaN")
+    return _DEPTH_MODES[mode], threshold
+
+
+def _depth_pair(depth_A, depth_B, T, K_A, K_B):
+    """-> contiguous depth_A (P,Ha,Wa), depth_B (P,Hb,Wb) fp32, T (P,3,4), K_A, K_B (P,3,3) fp64"""
+    _need_gpu(depth_A, depth_B, T, K_A, K_B)
+    if depth_A.dim() != 3 or depth_B.dim() != 3 or depth_A.shape[0] != depth_B.shape[0]:
+        raise ValueError(f"expected depth maps (P,H_A,W_A) and (P,H_B,W_B), got {tuple(depth_A.shape)} and {tuple(depth_B.shape)}")
+    P = depth_A.shape[0]
+    if T.shape not in ((P, 3, 4), (P, 4, 4)):
+        raise ValueError(f"expected a pose ({P},3,4) or ({P},4,4), got {tuple(T.shape)}")
+    for name, K in (("K_A", K_A), ("K_B", K_B)):
+        if K.shape != (P, 3, 3):
+            raise ValueError(f"{name}: expected ({P},3,3) intrinsics, got {tuple(K.shape)}")
+    return (depth_A.to(torch.float32).contiguous(), depth_B.to(torch.float32).contiguous(), T[:, :3, :4].to(torch.float64).contiguous(),
+            K_A.to(torch.float64).contiguous(), K_B.to(torch.float64).contiguous())
+
+
+def warp_kpts(kpts0, depth0, depth1, T_0to1, K0, K1, smooth_mask=False, return_relative_depth_error=False,
+              depth_interpolation_mode="bilinear", relative_depth_error_threshold=0.05):
+    """warp_kpts of the reference (romatch/utils/utils.py:358-455) on the device (csrc/depth_warp.hip): key-points of image 0 are
+    lifted by depth0, moved by T_0to1 and projected into image 1; a point is valid where depth0 has a depth, the projection lies
+    strictly inside image 1 and the depth of depth1 there agrees with the computed one to relative_depth_error_threshold.
+    kpts0: (P,N,2) normalised to [-1,1], or the first two columns of a (P,N,4) warp (read in place); depth0 (P,H0,W0), depth1
+    (P,H1,W1); T_0to1 (P,3,4) or (P,4,4); K0, K1 (P,3,3).  Key-points and depths are used as fp32 — what the reference's callers hold
+    before their .double() — and everything per point is fp64 as there.  depth_interpolation_mode: "bilinear", "nearest", or
+    "combined" (the nearest result where the bilinear one is not valid; the reference's own branch asks grid_sample for
+    'nearest-exact', which torch refuses, so "nearest" is what it uses here).
+    Returns (valid bool (P,N), x2 fp64 (P,N,2) normalised in image 1), or (relative depth error fp64 (P,N), x2) with
+    return_relative_depth_error.  smooth_mask is not implemented.  No host synchronisation.
+    Which key-points are read in place: fp32 ones that are contiguous, or whose strides are exactly (4 N, 4, 1) at an 8-byte aligned
+    address (the [..., :2] view of a contiguous (P,N,4) warp).  Anything else — fp64 or fp16 key-points, other strides, and views whose
+    size-1 dimensions carry a foreign stride — is first copied to contiguous fp32; the result is the same."""
+    if smooth_mask is not False:
+        raise NotImplementedError("warp_kpts: smooth_mask is not implemented on the device")
+    code, threshold = _depth_mode(depth_interpolation_mode, relative_depth_error_threshold)
+    _need_gpu(kpts0)
+    if kpts0.dim() != 3 or kpts0.shape[-1] != 2 or not kpts0.is_floating_point():
+        raise ValueError(f"expected floating-point key-points (P,N,2), got {tuple(kpts0.shape)} {kpts0.dtype}")
+    da, db, T, Ka, Kb = _depth_pair(depth0, depth1, T_0to1, K0, K1)
+    P, N = kpts0.shape[:2]
+    if P != da.shape[0] or N < 1:
+        raise ValueError(f"key-points {tuple(kpts0.shape)} do not match {da.shape[0]} depth maps")
+    x = kpts0.to(torch.float32)
+    stride = 4 if x.stride() == (4 * N, 4, 1) and x.data_ptr() % 8 == 0 else 2
+    if stride == 2:
+        x = x.contiguous()
+    x2 = torch.empty((P, N, 2), dtype=torch.float64, device=x.device)
+    valid = None if return_relative_depth_error else torch.empty((P, N), dtype=torch.uint8, device=x.device)
+    rel = torch.empty((P, N), dtype=torch.float64, device=x.device) if return_relative_depth_error else None
+    check(_lib.load().roma_warp_kpts(x.data_ptr(), stride, da.data_ptr(), db.data_ptr(), T.data_ptr(), Ka.data_ptr(), Kb.data_ptr(), P, N,
+                                     da.shape[1], da.shape[2], db.shape[1], db.shape[2], code, threshold, x2.data_ptr(),
+                                     None if valid is None else valid.data_ptr(), None if rel is None else rel.data_ptr(), _stream()),
+          "roma_warp_kpts")
+    return (rel if return_relative_depth_error else valid.bool()), x2
+
+
+def gt_warp_grid(B, H, W, device):
+    """The key-points get_gt_warp warps: the pixel centres of an H x W image, (B, H*W, 2) fp32 [x, y] — torch.linspace(-1 + 1/n,
+    1 - 1/n, n) in fp32 on the device per axis, as the reference builds them."""
+    gx = torch.linspace(-1 + 1 / W, 1 - 1 / W, W, device=device)
+    gy = torch.linspace(-1 + 1 / H, 1 - 1 / H, H, device=device)
+    return torch.stack((gx[None, :].expand(H, W), gy[:, None].expand(H, W)), dim=-1).reshape(1, H * W, 2).expand(B, H * W, 2).contiguous()
+
+
+def get_gt_warp(depth1, depth2, T_1to2, K1, K2, depth_interpolation_mode="bilinear", relative_depth_error_threshold=0.05, H=None,
+                W=None):
+    """get_gt_warp of the reference (utils.py:326-355): warp_kpts on the pixel centres of an H x W grid (default: the size of depth1).
+    Returns (x2 (B,H,W,2) fp64 normalised in image 2, prob (B,H,W) fp32: 1 where the warp is valid)."""
+    _depth_mode(depth_interpolation_mode, relative_depth_error_threshold)
+    _need_gpu(depth1)
+    if depth1.dim() != 3:
+        raise ValueError(f"expected a depth map (B,H,W), got {tuple(depth1.shape)}")
+    B = depth1.shape[0]
+    if H is None:
+        H, W = depth1.shape[1:]
+    mask, x2 = warp_kpts(gt_warp_grid(B, H, W, depth1.device), depth1, depth2, T_1to2, K1, K2,
+                         depth_interpolation_mode=depth_interpolation_mode, relative_depth_error_threshold=relative_depth_error_threshold)
+    return x2.reshape(B, H, W, 2), mask.float().reshape(B, H, W)
+
+
+def dense_match_metrics(warp, depth_A, depth_B, T_AtoB, K_A, K_B, *, depth_interpolation_mode="bilinear",
+                        relative_depth_error_threshold=0.05, return_maps=False):
+    """End-point error and PCK@1/3/5 px of a dense warp against the ground truth of two depth maps and a pose, in one pass
+    (csrc/depth_warp.hip): geometric_dist of the reference's MegadepthDenseBenchmark fused — the warp_kpts chain on columns 0-1 of every
+    pixel, the distance in pixels (of the warp's own H x W) between that and columns 2-3, and per-pair sums.
+    warp: (P,H,W,4) fp32 [x_A, y_A, predicted x_B, y_B] normalised; the left half warp[:, :, :W] of a symmetric (P,H,2W,4) result of
+    match() is read in place.  depth_A, depth_B, T_AtoB, K_A, K_B and the two options as warp_kpts.
+    Which warps are read in place: fp32 ones whose strides are exactly (H pitch, pitch, 4, 1) with pitch a multiple of 4 and >= 4 W, at
+    a 16-byte aligned address — a contiguous warp, or the left half above.  Anything else (another dtype, other strides, a size-1
+    dimension with a foreign stride) is first copied to contiguous fp32; the result is the same.
+    Returns a DenseMatchMetrics; return_maps adds the per-pixel distance and validity.  No host synchronisation, no atomics: the
+    result is bitwise reproducible and a pair's sums do not depend on the rest of the batch."""
+    code, threshold = _depth_mode(depth_interpolation_mode, relative_depth_error_threshold)
+    _need_gpu(warp)
+    if warp.dim() != 4 or warp.shape[-1] != 4 or not warp.is_floating_point():
+        raise ValueError(f"expected a floating-point warp (P,H,W,4), got {tuple(warp.shape)} {warp.dtype}")
+    da, db, T, Ka, Kb = _depth_pair(depth_A, depth_B, T_AtoB, K_A, K_B)
+    P, H, W = warp.shape[:3]
+    if P != da.shape[0] or H < 1 or W < 1:
+        raise ValueError(f"warp {tuple(warp.shape)} does not match {da.shape[0]} depth maps")
+    w = warp.to(torch.float32)
+    pitch = w.stride(1)
+    if w.stride() != (H * pitch, pitch, 4, 1) or pitch < 4 * W or pitch % 4 or w.data_ptr() % 16:
+        w = w.contiguous()
+        pitch = 4 * W
+    dev = w.device
+    nbytes = dense_metrics_workspace(P, H, W)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    epe_sum = torch.empty(P, dtype=torch.float64, device=dev)
+    counts = torch.empty((P, 4), dtype=torch.int64, device=dev)
+    gd = torch.empty((P, H, W), dtype=torch.float64, device=dev) if return_maps else None
+    valid = torch.empty((P, H, W), dtype=torch.uint8, device=dev) if return_maps else None
+    check(_lib.load().roma_dense_match_metrics(w.data_ptr(), pitch, da.data_ptr(), db.data_ptr(), T.data_ptr(), Ka.data_ptr(), Kb.data_ptr(),
+                                               P, H, W, da.shape[1], da.shape[2], db.shape[1], db.shape[2], code, threshold, ws.data_ptr(),
+                                               nbytes, epe_sum.data_ptr(), counts.data_ptr(), None if gd is None else gd.data_ptr(),
+                                               None if valid is None else valid.data_ptr(), _stream()), "roma_dense_match_metrics")
+    return DenseMatchMetrics(epe_sum, counts, gd, None if valid is None else valid.float())
+
+
+def geometric_dist(depth1, depth2, T_1to2, K1, K2, dense_matches):
+    """MegadepthDenseBenchmark.geometric_dist of the reference (megadepth_dense_benchmark.py:17-42), its five-tuple: (gd[prob == 1]
+    fp64, pck_1, pck_3, pck_5 fp32 scalars, prob (B,H,W) fp32).  Selecting gd[prob == 1] synchronises with the host, as it does in
+    the reference; dense_match_metrics is the call without that."""
+    m = dense_match_metrics(dense_matches, depth1, depth2, T_1to2, K1, K2, return_maps=True)
+    n = m.n_valid.sum().to(torch.float32)
+    return (m.gd[m.prob == 1], m.n_pck_1.sum().to(torch.float32) / n, m.n_pck_3.sum().to(torch.float32) / n,
+            m.n_pck_5.sum().to(torch.float32) / n, m.prob)
