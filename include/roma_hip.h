@@ -186,6 +186,31 @@ int roma_kde_density(const float* x, float* density, int N, int down, float std,
 int roma_race_keys(const float* p, const long* counter, float* keys, long N, float thresh, unsigned seed, unsigned stage,
                    void* stream);
 
+/* The k best items of each of P rows under the exponential race above, for sample_batch: row r ranks its N items by
+ * (key descending, c ascending), key = the roma_race_keys key of (p[r,i], thresh, seeds[r], stage, c) bit for bit and
+ * c = counter[r,i] or i when counter is NULL.  The c of one row must be distinct and below 2^32; the order is then total, so the
+ * selected set and its order do not depend on P, on the other rows, on launch geometry or on a library's handling of equal keys
+ * (thousands of items share a key: every weight above thresh is 1 and u has 24 bits; every weight <= 0 has key 0).
+ * Radix select over the 64-bit value  sortkey = monotone(key bits) << 32 | (0xFFFFFFFF - c),  11 bits per pass, one launch per
+ * pass (8 launches in all), keys recomputed from the hash in every pass; integer atomics only, no host synchronisation; the
+ * library allocates nothing.
+ *   p (P,N) fp32, counter (P,N) int64 or NULL, seeds (P) int64 (the low 32 bits are used), all device; 1 <= k <= N <= 2^24.
+ *   sel_key (P,k) int64: the selected items' sortkey with the top bit flipped, so that SIGNED descending order is draw order;
+ *   sel_idx (P,k) int64: their positions i, in the same slots.  The slots of a row are filled in arrival order: sort each row by
+ *   sel_key, descending, to get the draw order (the values of a row are distinct, so any sort gives the same result).
+ *   workspace: device, 8-byte aligned, at least roma_race_select_workspace(P, N, k) bytes (host function; < 0 on a bad shape);
+ *   need not be initialised. */
+long roma_race_select_workspace(int P, long N, int k);
+int roma_race_select(const float* p, const long* counter, const long* seeds, int P, long N, int k, float thresh, unsigned stage,
+                     long* sel_key, long* sel_idx, void* workspace, long workspace_bytes, void* stream);
+
+/* roma_kde_density for P independent sets of n points in one launch (the pair on the grid's second axis), same term arithmetic
+ * and summation order per query, so density[r] is bitwise what roma_kde_density gives for set r alone.  The points of set r are
+ * rows of x (P,N,4) fp32: row index[r,j] when index (P,n) int64 is given (out-of-range values are clamped into the pair), else
+ * row j (then N == n).  half_mode = 1 rounds the coordinates to fp16 in the load (no separate x.half() pass); density (P,n) fp32. */
+int roma_kde_density_batch(const float* x, const long* index, float* density, int P, long N, int n, int down, float std,
+                           int half_mode, void* stream);
+
 /* Nearest neighbours for RegressionMatcher.match_keypoints (matcher.py:576-591): idx[i] = arg min_j |q_i - r_j|^2 over 2-D points
  * (lowest j on exact ties).  The reference materialises cdist(x_A_to_B, x_B) and compares it with its row / column minima;
  * mutual nearest neighbours only need this arg-min in both directions.  q: (NQ,2), r: (NR,2) fp32; idx: (NQ) int32. */

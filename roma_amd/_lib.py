@@ -45,6 +45,10 @@ SIGNATURES = {
     "roma_kde_density": [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p],
     "roma_nn_argmin": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "roma_race_keys": [c_void_p, c_void_p, c_void_p, c_long, c_float, ctypes.c_uint, ctypes.c_uint, c_void_p],
+    "roma_race_select_workspace": [c_int, c_long, c_int],
+    "roma_race_select": [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_float, ctypes.c_uint, c_void_p, c_void_p, c_void_p, c_long,
+                         c_void_p],
+    "roma_kde_density_batch": [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_float, c_int, c_void_p],
     "roma_dwconv5x5_bn_relu": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "roma_resample_u8": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "roma_normalize_u8": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
@@ -99,7 +103,8 @@ SIGNATURES = {
     "roma_dense_match_metrics": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_int, ctypes.c_double, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
-_RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long, "roma_essential_workspace": c_long}
+_RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long, "roma_essential_workspace": c_long,
+             "roma_race_select_workspace": c_long}
 
 _lib = None
 

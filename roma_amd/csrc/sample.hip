@@ -5,29 +5,16 @@
 // sample modes (matcher.py:474-477), a counter-based uniform (a pure function of (seed, index): reproducible on a CPU
 // oracle, independent of launch geometry) and the key; the selection itself is a library top-k.
 #include "common.h"
+#include "sample_device.h"
 
 namespace roma {
 namespace {
 
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return h;
-}
-
 __global__ __launch_bounds__(256) void race_keys_kernel(const float* __restrict__ p, const long* __restrict__ counter,
                                                         float* __restrict__ keys, long N, float thresh, uint32_t seed, uint32_t stage) {
-  // the stream of one (seed, stage) pair: mixed non-linearly, so that neither seed + 1 nor the second draw of the same seed is a
-  // shifted copy of this one (round 2 hashed ctr * A + seed * B + C and ran the second draw at seed + 1)
-  const uint32_t stream = fmix32(seed ^ (stage * 0x9E3779B9u));
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long)gridDim.x * blockDim.x) {
-    float w = p[i];
-    if (thresh >= 0.f && w > thresh) w = 1.f;
-    const uint32_t ctr = (uint32_t)(counter ? counter[i] : i);             // the item's identity, not its position
-    const uint32_t h = fmix32(stream + ctr * 0x9E3779B1u);
-    const float u = ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);        // (0, 1), 24 bits, exact in fp32
-    const float e = -logf(u);
-    keys[i] = (w > 0.f) ? w / e : 0.f;
-  }
+  const uint32_t stream = race_stream(seed, stage);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long)gridDim.x * blockDim.x)
+    keys[i] = race_key(p[i], thresh, stream, (uint32_t)(counter ? counter[i] : i));   // sample_device.h: shared with sample_batch.hip
 }
 
 // nearest reference point of every query point (2-D, squared Euclidean distance, LOWEST index on exact ties) —

@@ -53,12 +53,46 @@ def gather_results(warp: torch.Tensor, certainty: torch.Tensor, num_pairs: int, 
     return full[..., :4].to(out_dtype[0]).contiguous(), full[..., 4].to(out_dtype[1]).contiguous()
 
 
-def match_sharded(match_fn: Callable, pairs: Sequence, dst: int = 0, group=None, wire_dtype=None):
-    """Run `match_fn(list_of_local_pairs) -> (warp, certainty)` on this rank's contiguous shard of `pairs` and gather."""
+def gather_matches(matches: torch.Tensor, certainty: torch.Tensor, num_pairs: int, dst: int = 0, group=None):
+    """Gather each rank's sampled matches (p_rank, num, 4) / (p_rank, num) — sample_batch's fixed-shape result — to `dst`, in pair
+    order: about 200 KB per pair at num = 10 000 on the links, where gather_results ships the 29.9 MB dense warp.  Uneven shards
+    are padded to the largest shard inside one packed (num, 5) record per pair, as gather_results pads them.  Returns
+    (matches, certainty) on dst, (None, None) elsewhere."""
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    if world == 1:
+        return matches, certainty
+    counts = [shard_range(num_pairs, world, r) for r in range(world)]
+    pmax = max(hi - lo for lo, hi in counts)
+    n, num = matches.shape[0], matches.shape[1]
+    wire = torch.promote_types(matches.dtype, certainty.dtype)
+    packed = torch.zeros((pmax, num, 5), dtype=wire, device=matches.device)
+    packed[:n, :, :4] = matches
+    packed[:n, :, 4] = certainty
+    parts = [torch.empty_like(packed) for _ in range(world)] if rank == dst else None
+    dist.gather(packed, parts, dst=dst, group=group)
+    if rank != dst:
+        return None, None
+    full = torch.cat([parts[r][: hi - lo] for r, (lo, hi) in enumerate(counts)], dim=0)
+    return full[..., :4].to(matches.dtype).contiguous(), full[..., 4].to(certainty.dtype).contiguous()
+
+
+def match_sharded(match_fn: Callable, pairs: Sequence, dst: int = 0, group=None, wire_dtype=None, gather: str = "dense",
+                  sample_fn: Optional[Callable] = None):
+    """Run `match_fn(list_of_local_pairs) -> (warp, certainty)` on this rank's contiguous shard of `pairs` and gather.
+    gather="matches": `sample_fn(warp, certainty) -> (matches (p,num,4), certainty (p,num))` (e.g. model.sample_batch) runs on
+    the local shard first and only the samples travel (gather_matches)."""
+    if gather not in ("dense", "matches"):
+        raise ValueError(f"gather must be 'dense' or 'matches', got {gather!r}")
+    if gather == "matches" and sample_fn is None:
+        raise ValueError("gather='matches' needs a sample_fn")
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     lo, hi = shard_range(len(pairs), world, rank)
     warp, cert = match_fn(list(pairs[lo:hi]))
+    if gather == "matches":
+        m, c = sample_fn(warp, cert)
+        return (m, c) if world == 1 else gather_matches(m, c, len(pairs), dst=dst, group=group)
     if world == 1:
         return warp, cert
     return gather_results(warp, cert, len(pairs), dst=dst, group=group, wire_dtype=wire_dtype)

@@ -593,6 +593,13 @@ class RegressionMatcher(nn.Module):
         bal = torch.topk(ops.race_keys(p, -1.0, seed, counter=good, stage=1), min(num, len(good_certainty))).indices
         return good_matches[bal], good_certainty[bal]
 
+    def sample_batch(self, matches, certainty, num=10000, seeds=None):
+        """sample() for P pairs in one call: matches (P,...,4), certainty (P,...) -> (P,k2,4), (P,k2), shapes fixed by the input
+        shapes (ops.sample_batch).  Row p is a pure function of (matches[p], certainty[p], seeds[p]) — equal keys are ranked by
+        item index, not by a library top-k — and equals sample(matches[p], certainty[p], num, seed=seeds[p]) wherever no two keys
+        tie.  seeds: P ints, a device int64 tensor, or None (P draws from torch's CPU generator).  No host synchronisation."""
+        return ops.sample_batch(matches, certainty, num, seeds, self.sample_mode, self.sample_thresh)
+
     # -- coordinates -----------------------------------------------------------------------------
     def to_pixel_coordinates(self, coords, H_A, W_A, H_B=None, W_B=None):
         if coords.shape[-1] == 2:

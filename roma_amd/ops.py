@@ -521,6 +521,105 @@ def race_keys(p, thresh=-1.0, seed=0, counter=None, stage=0):
     return keys
 
 
+def seed_tensor(seeds, P, device):
+    """(P,) int64 device seeds from a sequence of P ints, a tensor, or None (P draws from torch's CPU generator, as sample()
+    draws its one).  Host values travel through pinned memory without blocking, so nothing here waits for the device."""
+    if seeds is None:
+        seeds = torch.randint(0, 2 ** 31 - 1, (P,))
+    if not torch.is_tensor(seeds):
+        seeds = torch.tensor([int(s) & 0xFFFFFFFF for s in seeds], dtype=torch.int64)
+    seeds = seeds.reshape(-1).to(torch.int64)
+    if seeds.numel() != P:
+        raise ValueError(f"{P} pairs need {P} seeds, got {seeds.numel()}")
+    if not seeds.is_cuda:
+        seeds = seeds.pin_memory().to(device, non_blocking=True)
+    return seeds.contiguous()
+
+
+def race_select(p, k, thresh=-1.0, seeds=None, counter=None, stage=0):
+    """The k best items of every row of p (P,N) under the exponential race of race_keys, ranked by (key descending, counter
+    ascending) — a total order, so the (P,k) int64 result (positions in the row, in draw order) is unique: it does not depend on
+    P, the other rows or a library's tie handling.  Keys are bitwise race_keys(p[r], thresh, seeds[r], counter[r], stage).  A radix
+    select over the 64-bit (key, counter) value (include/roma_hip.h: roma_race_select), then a sort of the k distinct selected
+    values per row; no full sort or top-k of the P x N keys, no host synchronisation."""
+    _need_gpu(p, counter)
+    if p.dim() != 2:
+        raise ValueError("race_select expects (P,N) weights")
+    if seeds is None:
+        raise ValueError("race_select needs P seeds")
+    p = p.float().contiguous()
+    P, N = p.shape
+    k = int(k)
+    seeds = seed_tensor(seeds, P, p.device)
+    _need_gpu(seeds)
+    if counter is not None:
+        counter = counter.long().contiguous()
+        if counter.shape != p.shape:
+            raise ValueError("race_select: counter must have the shape of p")
+    lib = _lib.load()
+    nbytes = lib.roma_race_select_workspace(P, N, k)
+    if nbytes < 0:
+        check(int(nbytes), "roma_race_select_workspace")
+    ws = torch.empty((nbytes // 8 + 1,), dtype=torch.int64, device=p.device)
+    sel_key = torch.empty((P, k), dtype=torch.int64, device=p.device)
+    sel_idx = torch.empty((P, k), dtype=torch.int64, device=p.device)
+    check(lib.roma_race_select(_p(p), _p(counter), _p(seeds), P, N, k, float(thresh), int(stage) & 0xFFFFFFFF, _p(sel_key), _p(sel_idx),
+                               _p(ws), ws.numel() * 8, _stream()), "roma_race_select")
+    order = torch.sort(sel_key, dim=1, descending=True).indices           # k distinct values per row: any sort gives this order
+    return sel_idx.gather(1, order)
+
+
+def kde_batch(x, std=0.1, half=True, down=None, index=None):
+    """kde() for P point sets in one launch: x (P,n,4) -> (P,n), row r bitwise kde(x[r], std, half, down).  With index (P,n) int64
+    the points of set r are x[r, index[r]] of x (P,N,4): the gather, and the fp16 rounding of half=True, happen in the load."""
+    _need_gpu(x, index)
+    if x.dim() != 3 or x.shape[2] != 4:
+        raise ValueError("kde_batch expects (P,n,4) matches")
+    x = x.float().contiguous()
+    P, N = x.shape[:2]
+    n = N
+    if index is not None:
+        if index.dim() != 2 or index.shape[0] != P:
+            raise ValueError("kde_batch: index must be (P,n)")
+        index = index.long().contiguous()
+        n = index.shape[1]
+    dens = torch.empty((P, n), dtype=torch.float32, device=x.device)
+    check(_lib.load().roma_kde_density_batch(_p(x), _p(index), _p(dens), P, N, n, int(down or 1), float(std), 1 if half else 0, _stream()),
+          "roma_kde_density_batch")
+    return dens.half() if half else dens
+
+
+def sample_batch(matches, certainty, num, seeds=None, sample_mode="threshold_balanced", sample_thresh=0.05):
+    """sample() for P pairs with fixed output shapes: matches (P,...,4), certainty (P,...) -> (P,k2,4), (P,k2) with
+    k1 = min(e * num, N), e = 4 in the balanced modes else 1, and k2 = min(num, k1) in the balanced modes else k1.  Row r is a pure
+    function of (matches[r], certainty[r], seeds[r]): both selections rank by (key descending, item index ascending), keys and
+    densities are bitwise those of race_keys / kde, so where no two keys tie row r equals sample(matches[r], certainty[r], num,
+    seed=seeds[r]).  Two race_select calls, one gathering kde_batch, element-wise torch ops on (P,k) tensors; no host sync."""
+    _need_gpu(matches, certainty)
+    P = matches.shape[0]
+    matches = matches.reshape(P, -1, 4).float().contiguous()
+    certainty = certainty.reshape(P, -1).float().contiguous()
+    N = certainty.shape[1]
+    if matches.shape[1] != N:
+        raise ValueError("sample_batch: matches and certainty disagree on the number of items per pair")
+    seeds = seed_tensor(seeds, P, matches.device)
+    thresh = sample_thresh if "threshold" in sample_mode else -1.0
+    balanced = "balanced" in sample_mode
+    k1 = min((4 if balanced else 1) * num, N)
+    good = race_select(certainty, k1, thresh, seeds)
+    good_certainty = certainty.gather(1, good)
+    if thresh >= 0:
+        good_certainty = torch.where(good_certainty > thresh, torch.ones_like(good_certainty), good_certainty)
+    if not balanced:
+        return matches.gather(1, good[..., None].expand(-1, -1, 4)), good_certainty
+    density = kde_batch(matches, std=0.1, half=True, down=1, index=good)     # fp16, like sample()
+    p = 1 / (density + 1)                                                     # fp16 ops, as in sample()
+    p = torch.where(density < 10, torch.full_like(p, 1e-7), p)                # 1e-7 is 1.19e-7 in fp16
+    bal = race_select(p, min(num, k1), -1.0, seeds, counter=good, stage=1)
+    sel = good.gather(1, bal)
+    return matches.gather(1, sel[..., None].expand(-1, -1, 4)), good_certainty.gather(1, bal)
+
+
 def nn_argmin(q, r):
     """idx[i] = arg min_j |q_i - r_j|^2 for 2-D point sets q (NQ,2), r (NR,2) -> (NQ,) int64; the two arg-min vectors that the
     mutual-nearest-neighbour test of match_keypoints (matcher.py:585-588) needs, without the |q| x |r| cdist matrix."""

@@ -159,6 +159,10 @@ class TinyRoMa(nn.Module):
         bal = torch.topk(ops.race_keys(p, -1.0, seed, counter=good, stage=1), min(num, len(gc))).indices
         return gm[bal], gc[bal]
 
+    def sample_batch(self, matches, certainty, num=5_000, seeds=None):
+        """RegressionMatcher.sample_batch with this model's default `num`."""
+        return ops.sample_batch(matches, certainty, num, seeds, self.sample_mode, self.sample_thresh)
+
 
 class XFeatBackbone(nn.Module):
     """The XFeat backbone TOPOLOGY ("XFeat: Accelerated Features for Lightweight Image Matching", CVPR 2024) with the
