@@ -56,6 +56,11 @@ KIND_E = 2                            # this module's name for the essential est
 _SMIN = {KIND_F: 7, KIND_H: 4, KIND_E: 5}
 _SLOTS = {KIND_F: 3, KIND_H: 1, KIND_E: 10}
 _WORKSPACE_LIMIT = 192 << 20          # workspace bytes of one call; larger batches run in chunks of pairs that share it
+# The C entry points of an estimator: (workspace function, hypotheses entry, select entry, workspace regions, calibrated).  F and H share
+# theirs, which take the kind first; E has its own (calibrated), which take K_A, K_B behind the points and lay out one more region.
+_RANSAC = ("roma_ransac_workspace", "roma_ransac_hypotheses_ex", "roma_ransac_select_ex", 9, False)
+_ENTRIES = {KIND_F: _RANSAC, KIND_H: _RANSAC,
+            KIND_E: ("roma_essential_workspace", "roma_essential_hypotheses_ex", "roma_essential_select_ex", 10, True)}
 
 
 def _kind(model):
@@ -89,6 +94,17 @@ def _points(x_A, x_B, kind):
     return xa, xb, single
 
 
+def _mask(mask, P, N, points=None):
+    """The optional mask of a call, bool / uint8 -> contiguous (P,N) uint8, or None.  points: the caller's x_A, (N,2) or (P,N,2), whose
+    (N,) or (P,N) the mask must have; None where the caller has checked the shape itself."""
+    if mask is None:
+        return None
+    _need_gpu(mask)
+    if points is not None and mask.shape != ((N,) if points.dim() == 2 else (P, N)):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(points.shape)}")
+    return mask.reshape(P, N).to(torch.uint8).contiguous()
+
+
 def _seed(seed):
     # like RegressionMatcher.sample: torch's CPU generator, no device sync
     return int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if seed is None else int(seed) & 0xFFFFFFFF
@@ -115,16 +131,11 @@ def _args(threshold, max_iters, lo_iters):
 def workspace_layout(kind, P, N, iters):
     """(total bytes, [region offsets]) of the workspace (include/roma_hip.h: the 9 regions of roma_ransac_workspace, the 10 of
     roma_essential_workspace for KIND_E)."""
-    if kind == KIND_E:
-        off = (ctypes.c_long * 10)()
-        total = _lib.load().roma_essential_workspace(P, N, iters, ctypes.cast(off, ctypes.c_void_p))
-        what = "roma_essential_workspace"
-    else:
-        off = (ctypes.c_long * 9)()
-        total = _lib.load().roma_ransac_workspace(kind, P, N, iters, ctypes.cast(off, ctypes.c_void_p))
-        what = "roma_ransac_workspace"
+    workspace, _, _, regions, calibrated = _ENTRIES[kind]
+    off = (ctypes.c_long * regions)()
+    total = getattr(_lib.load(), workspace)(*(() if calibrated else (kind,)), P, N, iters, ctypes.cast(off, ctypes.c_void_p))
     if total < 0:
-        check(int(total), what)
+        check(int(total), workspace)
     return int(total), list(off)
 
 
@@ -161,15 +172,12 @@ def _inverse_intrinsics(K):
     return T
 
 
-def _hypotheses(xa, xb, kind, threshold, iters, seed, p0, ws, K=None, score=_lib.SCORE_MSAC):
+def _hypotheses(xa, xb, kind, threshold, iters, seed, p0, ws, K=(), score=_lib.SCORE_MSAC):
+    """K: the (K_A, K_B) of these pairs for KIND_E, nothing for F and H"""
     P, N = xa.shape[0], xa.shape[1]
-    if kind == KIND_E:
-        check(_lib.load().roma_essential_hypotheses_ex(xa.data_ptr(), xb.data_ptr(), K[0].data_ptr(), K[1].data_ptr(), P, N, iters,
-                                                       float(threshold), score, seed, p0, ws.data_ptr(), ws.numel(), _stream()),
-              "roma_essential_hypotheses_ex")
-        return
-    check(_lib.load().roma_ransac_hypotheses_ex(kind, xa.data_ptr(), xb.data_ptr(), P, N, iters, float(threshold), score, seed, p0,
-                                                ws.data_ptr(), ws.numel(), _stream()), "roma_ransac_hypotheses_ex")
+    _, entry, _, _, calibrated = _ENTRIES[kind]
+    check(getattr(_lib.load(), entry)(*(() if calibrated else (kind,)), xa.data_ptr(), xb.data_ptr(), *(k.data_ptr() for k in K), P, N, iters,
+                                      float(threshold), score, seed, p0, ws.data_ptr(), ws.numel(), _stream()), entry)
 
 
 def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_B=None, scoring="msac"):
@@ -177,8 +185,8 @@ def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_
     _args(threshold, max_iters, lo_iters)
     xa, xb, single = _points(x_A, x_B, kind)
     P, N = xa.shape[0], xa.shape[1]
-    if kind == KIND_E:
-        Ka, Kb = _intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")
+    _, _, select, _, calibrated = _ENTRIES[kind]
+    K = (_intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")) if calibrated else ()
     iters, seed = int(max_iters), _seed(seed)
     model = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
     mask = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
@@ -188,17 +196,11 @@ def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_
     total, _ = workspace_layout(kind, max(b - a for a, b in chunks), N, iters)
     ws = torch.empty((total,), dtype=torch.uint8, device=xa.device)
     for a, b in chunks:
-        ca, cb = xa[a:b], xb[a:b]
-        if kind == KIND_E:
-            _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws, (Ka[a:b], Kb[a:b]), score)
-            check(lib.roma_essential_select_ex(ca.data_ptr(), cb.data_ptr(), Ka[a:b].data_ptr(), Kb[a:b].data_ptr(), b - a, N, iters,
-                                               float(threshold), score, int(lo_iters), ws.data_ptr(), total, model[a:b].data_ptr(),
-                                               mask[a:b].data_ptr(), _stream()), "roma_essential_select_ex")
-            continue
-        _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws, None, score)
-        check(lib.roma_ransac_select_ex(kind, ca.data_ptr(), cb.data_ptr(), b - a, N, iters, float(threshold), score, int(lo_iters),
-                                        ws.data_ptr(), total, model[a:b].data_ptr(), mask[a:b].data_ptr(), _stream()),
-              "roma_ransac_select_ex")
+        ca, cb, Kc = xa[a:b], xb[a:b], tuple(k[a:b] for k in K)
+        _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws, Kc, score)
+        check(getattr(lib, select)(*(() if calibrated else (kind,)), ca.data_ptr(), cb.data_ptr(), *(k.data_ptr() for k in Kc), b - a, N,
+                                   iters, float(threshold), score, int(lo_iters), ws.data_ptr(), total, model[a:b].data_ptr(),
+                                   mask[a:b].data_ptr(), _stream()), select)
     mask = mask.bool()
     return (model[0], mask[0]) if single else (model, mask)
 
@@ -267,12 +269,7 @@ def recover_pose(E, x_A, x_B, K_A, K_B, mask=None):
         raise ValueError(f"E {tuple(E.shape)} does not match the points {tuple(x_A.shape)}")
     Ka, Kb = _intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")
     e = E.reshape(P, 3, 3).to(torch.float64).contiguous()
-    m = None
-    if mask is not None:
-        _need_gpu(mask)
-        if mask.shape != ((N,) if single else (P, N)):
-            raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
-        m = mask.reshape(P, N).to(torch.uint8).contiguous()
+    m = _mask(mask, P, N, x_A)
     R = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
     t = torch.empty((P, 3), dtype=torch.float64, device=xa.device)
     count = torch.empty((P,), dtype=torch.int32, device=xa.device)
@@ -314,13 +311,28 @@ def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, 
     return recover_pose(Kb.transpose(-1, -2) @ F @ Ka, kpts0, kpts1, Ka, Kb, mask)
 
 
-def _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask):
-    """refine_pose on batched outputs: (R (P,3,3), t (P,3), mask (P,N) bool, cost (P,) fp64, count (P,) int32, steps (P,) int32), single"""
-    _need_gpu(R, t)
+def _refine_args(threshold, iters):
     if not float(threshold) > 0:
         raise ValueError(f"threshold must be positive, got {threshold}")
     if int(iters) < 0:
         raise ValueError(f"iters must be >= 0, got {iters}")
+
+
+def _refined(res, info, single, return_info):
+    """What a refine_* call returns from its batched outputs: res = (the model(s), mask), of the one pair where the call was for one, and
+    on request the dict info = (cost, count, steps)"""
+    if single:
+        res = tuple([v[0] for v in res])
+    if not return_info:
+        return res
+    cost, count, steps = info
+    return res + ({"cost": cost[0], "count": count[0], "steps": steps[0]} if single else {"cost": cost, "count": count, "steps": steps},)
+
+
+def _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask):
+    """refine_pose on batched outputs: (R (P,3,3), t (P,3), mask (P,N) bool), (cost (P,) fp64, count (P,) int32, steps (P,) int32), single"""
+    _need_gpu(R, t)
+    _refine_args(threshold, iters)
     xa, xb, single = _points(x_A, x_B, KIND_E)
     P, N = xa.shape[0], xa.shape[1]
     if R.shape != ((3, 3) if single else (P, 3, 3)) or t.shape != ((3,) if single else (P, 3)):
@@ -328,23 +340,19 @@ def _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask):
     Ka, Kb = _intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")
     r0 = R.reshape(P, 3, 3).to(torch.float64).contiguous()
     t0 = t.reshape(P, 3).to(torch.float64).contiguous()
-    m = None
-    if mask is not None:
-        _need_gpu(mask)
-        if mask.shape != ((N,) if single else (P, N)):
-            raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
-        m = mask.reshape(P, N).to(torch.uint8).contiguous()
-    Ro = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
-    to = torch.empty((P, 3), dtype=torch.float64, device=xa.device)
-    out = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
-    cost = torch.empty((P,), dtype=torch.float64, device=xa.device)
-    count = torch.empty((P,), dtype=torch.int32, device=xa.device)
-    steps = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    m = _mask(mask, P, N, x_A)
+    dev = xa.device
+    Ro = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    to = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
+    cost = torch.empty((P,), dtype=torch.float64, device=dev)
+    count = torch.empty((P,), dtype=torch.int32, device=dev)
+    steps = torch.empty((P,), dtype=torch.int32, device=dev)
     check(_lib.load().roma_refine_pose(xa.data_ptr(), xb.data_ptr(), Ka.data_ptr(), Kb.data_ptr(), r0.data_ptr(), t0.data_ptr(),
                                        None if m is None else m.data_ptr(), P, N, float(threshold), int(iters), Ro.data_ptr(),
                                        to.data_ptr(), out.data_ptr(), cost.data_ptr(), count.data_ptr(), steps.data_ptr(), _stream()),
           "roma_refine_pose")
-    return (Ro, to, out.bool(), cost, count, steps), single
+    return (Ro, to, out.bool()), (cost, count, steps), single
 
 
 def refine_pose(R, t, x_A, x_B, K_A, K_B, threshold, iters=15, mask=None, return_info=False):
@@ -357,22 +365,14 @@ def refine_pose(R, t, x_A, x_B, K_A, K_B, threshold, iters=15, mask=None, return
     truncated cost of the returned pose), count (int32, its inliers), steps (int32, the steps kept).  A step is kept only if it
     lowers the cost, so the returned pose never has a higher cost than the given one; a pair that cannot be refined (fewer than 5
     weighted matches, a singular normal matrix, a pose that is not finite) gets its pose back unchanged."""
-    (Ro, to, out, cost, count, steps), single = _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask)
-    res = (Ro[0], to[0], out[0]) if single else (Ro, to, out)
-    if not return_info:
-        return res
-    info = {"cost": cost, "count": count, "steps": steps}
-    return res + ({k: v[0] for k, v in info.items()} if single else info,)
+    return _refined(*_refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask), return_info)
 
 
 def _refine_model(M, x_A, x_B, kind, least, entry, threshold, iters, mask, return_info):
     """what refine_fundamental and refine_homography run alike: the checks, the outputs and the call of the C entry point `entry`"""
     name = "F" if kind == KIND_F else "H"
     _need_gpu(M)
-    if not float(threshold) > 0:
-        raise ValueError(f"threshold must be positive, got {threshold}")
-    if int(iters) < 0:
-        raise ValueError(f"iters must be >= 0, got {iters}")
+    _refine_args(threshold, iters)
     xa, xb, single = _points(x_A, x_B, kind)
     P, N = xa.shape[0], xa.shape[1]
     if N < least:
@@ -380,26 +380,17 @@ def _refine_model(M, x_A, x_B, kind, least, entry, threshold, iters, mask, retur
     if M.shape != ((3, 3) if single else (P, 3, 3)):
         raise ValueError(f"{name} {tuple(M.shape)} does not match the points {tuple(x_A.shape)}")
     m0 = M.reshape(P, 3, 3).to(torch.float64).contiguous()
-    m = None
-    if mask is not None:
-        _need_gpu(mask)
-        if mask.shape != ((N,) if single else (P, N)):
-            raise ValueError(f"mask {tuple(mask.shape)} does not match the points {tuple(x_A.shape)}")
-        m = mask.reshape(P, N).to(torch.uint8).contiguous()
-    Mo = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
-    out = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
-    cost = torch.empty((P,), dtype=torch.float64, device=xa.device)
-    count = torch.empty((P,), dtype=torch.int32, device=xa.device)
-    steps = torch.empty((P,), dtype=torch.int32, device=xa.device)
+    m = _mask(mask, P, N, x_A)
+    dev = xa.device
+    Mo = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
+    cost = torch.empty((P,), dtype=torch.float64, device=dev)
+    count = torch.empty((P,), dtype=torch.int32, device=dev)
+    steps = torch.empty((P,), dtype=torch.int32, device=dev)
     check(getattr(_lib.load(), entry)(xa.data_ptr(), xb.data_ptr(), m0.data_ptr(), None if m is None else m.data_ptr(), P, N,
                                       float(threshold), int(iters), Mo.data_ptr(), out.data_ptr(), cost.data_ptr(), count.data_ptr(),
                                       steps.data_ptr(), _stream()), entry)
-    out = out.bool()
-    res = (Mo[0], out[0]) if single else (Mo, out)
-    if not return_info:
-        return res
-    info = {"cost": cost, "count": count, "steps": steps}
-    return res + ({k: v[0] for k, v in info.items()} if single else info,)
+    return _refined((Mo, out.bool()), (cost, count, steps), single, return_info)
 
 
 def refine_fundamental(F, x_A, x_B, threshold=3.0, iters=15, mask=None, return_info=False):
@@ -505,9 +496,8 @@ def estimate_relative_pose(kpts0, kpts1, camera0, camera1, ransac_opt=None, *, s
     K1 = torch.tensor(K1, dtype=torch.float64).to(kpts0.device)
     E, emask = find_essential(kpts0, kpts1, K0, K1, thr, max_iters=int(opt["max_iterations"]), seed=seed, scoring=scoring)
     R0, t0, mask0 = recover_pose(E, kpts0, kpts1, K0, K1, emask)
-    (R, t, mask, cost, count, steps), single = _refine(R0, t0, kpts0, kpts1, K0, K1, thr, int(opt["refine_iterations"]), None)
-    if single:
-        R, t, mask, cost, count, steps = R[0], t[0], mask[0], cost[0], count[0], steps[0]
+    R, t, mask, refined = refine_pose(R0, t0, kpts0, kpts1, K0, K1, thr, int(opt["refine_iterations"]), return_info=True)
+    cost, count, steps = refined["cost"], refined["count"], refined["steps"]
     keep = mask0.sum(-1) >= int(opt["min_inliers"])                  # on the device: no host synchronisation
     R = torch.where(keep[..., None, None], R, R0)
     t = torch.where(keep[..., None], t, t0)
@@ -576,7 +566,7 @@ def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=100
         _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, K, score)
         T = _inverse_intrinsics(torch.stack(K, 1))
     else:
-        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, None, score)
+        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, (), score)
         norm = _view(ws, off, 0, torch.float64, (P, 2, 4))
         T = torch.zeros((P, 2, 3, 3), dtype=torch.float64, device=xa.device)
         T[:, :, 0, 0] = norm[:, :, 2]
@@ -657,10 +647,7 @@ def _triangulate(m, to_px, R, t, K_A, K_B, single, code, max_reproj, max_cos, ma
     m = m.to(torch.float32).contiguous()
     Ka, Kb = _intrinsics(K_A, P, m.device, "K_A"), _intrinsics(K_B, P, m.device, "K_B")
     Rp, tp = _pose(R, t, P, single, m.device)
-    mk = None
-    if mask is not None:
-        _need_gpu(mask)
-        mk = mask.reshape(P, N).to(torch.uint8).contiguous()
+    mk = _mask(mask, P, N)                                    # triangulate has checked its shape; depth_from_warp built it
     f32 = dict(dtype=torch.float32, device=m.device)
     points = torch.empty((P, N, 3), **f32)
     depth_a, depth_b = torch.empty((P, N), **f32), torch.empty((P, N), **f32)

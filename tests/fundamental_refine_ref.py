@@ -12,19 +12,13 @@ from __future__ import annotations
 import numpy as np
 
 from tests import geometry_ref as G
+from tests.lm_ref import ACCEPT_REL, LAMBDA0, LAMBDA_MIN, cholesky_solve, same_bits, schedule, usable  # noqa: F401  (shared by the three)
 from tests.pose_refine_ref import exp_so3
 
-LAMBDA0, LAMBDA_MIN = 1e-3, 1e-10
-ACCEPT_REL = 1e-12                 # a step is kept when cost' < cost * (1 - ACCEPT_REL): strictly lower, by more than rounding
 MIN_MATCHES = 8
 RANK_TOL = 1e-14                   # sigma_2^2 <= RANK_TOL sigma_1^2: no second singular value (the eigenvalues carry ~eps sigma_1^2)
 JACOBI_SWEEPS = 10
 NPAR = 7
-
-
-def usable(xa, xb, mask=None):
-    ok = G.usable(xa, xb)
-    return ok if mask is None else ok & np.asarray(mask, bool)
 
 
 def normalisation(xa, xb, ok):
@@ -151,31 +145,6 @@ def normal_equations(U, s, V, TA, TB, xa, xb, thr, ok):
     return J[w].T @ J[w], J[w].T @ r[w]
 
 
-def cholesky_solve(A, lam, g):
-    """delta of (A + lam diag A) delta = -g by Cholesky; None on a pivot that is not positive (or not finite)"""
-    n = len(g)
-    M = A + lam * np.diag(np.diag(A))
-    L = np.zeros((n, n))
-    for j in range(n):
-        p = M[j, j] - L[j, :j] @ L[j, :j]
-        if not p > 0.0 or not np.isfinite(p):
-            return None
-        L[j, j] = np.sqrt(p)
-        for i in range(j + 1, n):
-            L[i, j] = (M[i, j] - L[i, :j] @ L[j, :j]) / L[j, j]
-    y = np.zeros(n)
-    for i in range(n):
-        y[i] = (-g[i] - L[i, :i] @ y[:i]) / L[i, i]
-    x = np.zeros(n)
-    for i in range(n - 1, -1, -1):
-        x[i] = (y[i] - L[i + 1:, i] @ x[i + 1:]) / L[i, i]
-    return x
-
-
-def _same_bits(a, b):
-    return np.asarray(a, float).tobytes() == np.asarray(b, float).tobytes()
-
-
 def refine(F0, xa, xb, thr, iters=15, mask=None):
     """One pair, pixels (N,2).  Returns a dict: F, mask, cost, count, steps (kept), costs (the cost of the input and after every kept
     step), cost0 (of the input as given).  Without a kept step — and with fewer than 8 weighted matches, a Cholesky pivot that is not
@@ -191,26 +160,17 @@ def refine(F0, xa, xb, thr, iters=15, mask=None):
         fac = factorise(F0, TA, TB)
     if fac is None:
         return start
-    U, s, V = fac
-    F, lam, steps, costs, eqs = F0, LAMBDA0, 0, [cost], None
-    for _ in range(iters):
-        if eqs is None:
-            eqs = normal_equations(U, s, V, TA, TB, xa, xb, thr, ok)
-        delta = cholesky_solve(eqs[0], lam, eqs[1])
-        if delta is None:
-            return start
+
+    def propose(state, delta):
+        U, s, V = state[:3]
         Uc, sc, Vc = step(U, s, V, delta)
-        if _same_bits(Uc, U) and _same_bits(Vc, V) and _same_bits(sc, s):
-            break                                          # the step moved nothing, and no later one will
-        Fc = pixel_model(Uc, sc, Vc, TA, TB)
-        c2, n2, w2, _ = cost_of(Fc, xa, xb, thr, ok)
-        if c2 < cost * (1.0 - ACCEPT_REL):
-            U, s, V, F, cost, cnt, w, eqs = Uc, sc, Vc, Fc, c2, n2, w2, None
-            lam = max(lam / 10.0, LAMBDA_MIN)
-            steps += 1
-            costs.append(cost)
-        else:
-            lam *= 10.0
-    if steps == 0:
+        if same_bits(Uc, U) and same_bits(Vc, V) and same_bits(sc, s):
+            return None
+        return Uc, sc, Vc, pixel_model(Uc, sc, Vc, TA, TB)
+
+    out = schedule((*fac, F0), cost, cnt, w, iters, lambda state, _: normal_equations(*state[:3], TA, TB, xa, xb, thr, ok), propose,
+                   lambda state: (*cost_of(state[3], xa, xb, thr, ok)[:3], None))
+    if out is None:
         return start
+    (_, _, _, F), cost, cnt, w, steps, costs = out
     return dict(F=F, mask=w, cost=cost, count=cnt, steps=steps, costs=costs, cost0=costs[0])

@@ -6,7 +6,11 @@ can be instantiated on either side and loaded with the same recipe weights (refe
 """
 from __future__ import annotations
 
+import ctypes
+import functools
 import os
+import re
+import subprocess
 
 import numpy as np
 import torch
@@ -15,6 +19,7 @@ import torch.nn as nn
 from tests.golden import cases, recipes as R
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def golden(name):
@@ -66,3 +71,56 @@ def full_model_weights(model_state_shapes, vit_state_shapes, seed=0):
 
 def asset(name):
     return os.path.join(GOLDEN, "assets", name)
+
+
+# ------------------------------------------------------------------------------------------ plumbing of the geometry tests
+def dev(a, device="cuda:0"):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
+def to_np(*tensors):
+    return [t.cpu().numpy() for t in tensors]
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_resources(hip_file, *extra_flags):
+    """The compiler's resource report of roma_amd/csrc/<hip_file> for gfx950 (what tools/kres.sh wraps): {kernel: {field: int}}.
+    Compiled once per (file, flags) and process; callers read the result and leave it as it is."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    assert os.path.exists(hipcc), f"{hipcc} is missing: the resource report needs the compiler"
+    src = os.path.join(ROOT, "roma_amd", "csrc", hip_file)
+    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
+                        "-Rpass-analysis=kernel-resource-usage", *extra_flags], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    kernels, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark:\s+Function Name: (\S+)", line)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+    return kernels
+
+
+def check_refine_entry_point_validates_arguments(entry, bind, least, null, misaligned):
+    """The assertions the three test_refine_*_entry_point_validates_arguments_without_a_gpu share.  bind(lib, a) returns the test's own
+    call(**kw) of the C entry point `entry`, every pointer defaulting to the 16-byte aligned host buffer a, with keywords for the
+    pointers named in `null` and `misaligned` and for P, N, thr, iters.  The entry must refuse, by code and message: a null pointer in
+    each argument of `null`, P = 0, N = least - 1, a threshold that is not positive, a negative iters, and a pointer that is not
+    16-byte aligned in each argument of `misaligned`."""
+    from roma_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_double * 32)()
+    call = bind(lib, ctypes.cast(buf, ctypes.c_void_p))
+    for kw in null:
+        assert call(**{kw: None}) == _lib.ROMA_E_ARG and (entry + ": null pointer").encode() in lib.roma_last_error()
+    assert call(P=0) == _lib.ROMA_E_SHAPE and b"bad shape" in lib.roma_last_error()
+    assert call(N=least - 1) == _lib.ROMA_E_SHAPE and f"need at least {least}".encode() in lib.roma_last_error()
+    for thr in (0.0, -1.0, float("nan")):
+        assert call(thr=thr) == _lib.ROMA_E_ARG and b"threshold" in lib.roma_last_error()
+    assert call(iters=-1) == _lib.ROMA_E_ARG and b"iters" in lib.roma_last_error()
+    odd = ctypes.c_void_p(ctypes.addressof(buf) + 8)
+    for kw in misaligned:
+        assert call(**{kw: odd}) == _lib.ROMA_E_ALIGN and b"16-byte" in lib.roma_last_error()

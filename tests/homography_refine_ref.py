@@ -12,10 +12,8 @@ from __future__ import annotations
 import numpy as np
 
 from tests import geometry_ref as G
-from tests.fundamental_refine_ref import cholesky_solve, normalisation, usable  # noqa: F401  (the same for both refinements)
+from tests.lm_ref import ACCEPT_REL, LAMBDA0, LAMBDA_MIN, cholesky_solve, same_bits, schedule, usable  # noqa: F401  (shared by the three)
 
-LAMBDA0, LAMBDA_MIN = 1e-3, 1e-10
-ACCEPT_REL = 1e-12                 # a step is kept when cost' < cost * (1 - ACCEPT_REL): strictly lower, by more than rounding
 MIN_MATCHES = 4
 NPAR = 8
 
@@ -95,10 +93,6 @@ def normal_equations(Hh, k, xah, xbh, thr_h, ok):
     return Jw.T @ Jw, Jw.T @ rw
 
 
-def _same_bits(a, b):
-    return np.asarray(a, float).tobytes() == np.asarray(b, float).tobytes()
-
-
 def refine(H0, xa, xb, thr, iters=15, mask=None):
     """One pair, pixels (N,2).  Returns a dict: H, mask, cost, count, steps (kept), costs (the cost of the input and after every kept
     step), cost0 (of the input as given).  Without a kept step — and with fewer than 4 weighted matches, a Cholesky pivot that is not
@@ -115,31 +109,23 @@ def refine(H0, xa, xb, thr, iters=15, mask=None):
     if not np.isfinite(Hh).all() or not Hh.any():
         return start
     thr_h = thr * sB
-    H, lam, steps, costs, eqs, k = H0, LAMBDA0, 0, [cost], None, 0
-    for _ in range(iters):
-        if eqs is None:
-            k = held_entry(Hh)
-            eqs = normal_equations(Hh, k, xah, xbh, thr_h, ok)
-        delta = cholesky_solve(eqs[0], lam, eqs[1])
-        if delta is None:
-            return start
+
+    def propose(state, delta):
+        Hh, _, k = state
         d = np.zeros(9)
         d[np.arange(9) != k] = delta
-        if _same_bits(Hh + d.reshape(3, 3), Hh):
-            break                                          # the step moved nothing, and no later one will
+        if same_bits(Hh + d.reshape(3, 3), Hh):
+            return None
         Hc = step(Hh, k, delta)
         with np.errstate(all="ignore"):
-            Fc = pixel_model(Hc, TA, TB)
-        c2, n2, w2, _ = cost_of(Fc, xa, xb, thr, ok)
-        if c2 < cost * (1.0 - ACCEPT_REL):
-            Hh, H, cost, cnt, w, eqs = Hc, Fc, c2, n2, w2, None
-            lam = max(lam / 10.0, LAMBDA_MIN)
-            steps += 1
-            costs.append(cost)
-        else:
-            lam *= 10.0
-    if steps == 0:
+            return Hc, pixel_model(Hc, TA, TB), held_entry(Hc)
+
+    # a state: (H^, the model in pixels, the entry of H^ that its equations hold)
+    out = schedule((Hh, H0, held_entry(Hh)), cost, cnt, w, iters, lambda state, _: normal_equations(state[0], state[2], xah, xbh, thr_h, ok),
+                   propose, lambda state: (*cost_of(state[1], xa, xb, thr, ok)[:3], None))
+    if out is None:
         return start
+    (_, H, _), cost, cnt, w, steps, costs = out
     return dict(H=H, mask=w, cost=cost, count=cnt, steps=steps, costs=costs, cost0=costs[0])
 
 

@@ -12,9 +12,8 @@ import numpy as np
 
 from tests import geometry_ref as G
 from tests import pose_ref as PR
+from tests.lm_ref import ACCEPT_REL, LAMBDA0, LAMBDA_MIN, cholesky_solve, schedule, usable  # noqa: F401  (the schedule the three refinements share)
 
-LAMBDA0, LAMBDA_MIN = 1e-3, 1e-10
-ACCEPT_REL = 1e-12                 # a step is kept when cost' < cost * (1 - ACCEPT_REL): strictly lower, by more than rounding
 MIN_MATCHES = 5
 EXP_TERMS = 10
 
@@ -84,11 +83,6 @@ def residuals(R, t, xh, xh2, jacobian=False):
     return r, J.T
 
 
-def usable(xh, xh2, mask=None):
-    ok = np.isfinite(xh).all(-1) & np.isfinite(xh2).all(-1)
-    return ok if mask is None else ok & np.asarray(mask, bool)
-
-
 def evaluate(R, t, xh, xh2, thr, ok):
     """-> (A = J^T J (5,5), g = J^T r (5,), cost, inlier count, inlier mask, r^2) over the usable matches `ok`"""
     r, J = residuals(R, t, xh, xh2, jacobian=True)
@@ -109,26 +103,6 @@ def truncated_cost(R, t, xh, xh2, thr, ok=None):
         return float(np.where(r2 < thr * thr, r2, thr * thr)[ok].sum())
 
 
-def cholesky_solve(A, lam, g):
-    """delta of (A + lam diag A) delta = -g by Cholesky; None on a pivot that is not positive (or not finite)"""
-    M = A + lam * np.diag(np.diag(A))
-    L = np.zeros((5, 5))
-    for j in range(5):
-        p = M[j, j] - L[j, :j] @ L[j, :j]
-        if not p > 0.0 or not np.isfinite(p):
-            return None
-        L[j, j] = np.sqrt(p)
-        for i in range(j + 1, 5):
-            L[i, j] = (M[i, j] - L[i, :j] @ L[j, :j]) / L[j, j]
-    y = np.zeros(5)
-    for i in range(5):
-        y[i] = (-g[i] - L[i, :i] @ y[:i]) / L[i, i]
-    x = np.zeros(5)
-    for i in range(4, -1, -1):
-        x[i] = (y[i] - L[i + 1:, i] @ x[i + 1:]) / L[i, i]
-    return x
-
-
 def refine(R0, t0, xa, xb, KA, KB, thr, iters=15, mask=None):
     """One pair, pixels (N,2).  Returns a dict: R, t, mask, cost, count, steps (accepted), costs (the cost after the start and after
     every accepted step), cost0 (of the input pose).  A failure (fewer than 5 weighted matches, a Cholesky pivot that is not
@@ -145,22 +119,19 @@ def refine(R0, t0, xa, xb, KA, KB, thr, iters=15, mask=None):
     start = dict(R=R0, t=t0, mask=w, cost=cost, count=cnt, steps=0, costs=[cost], cost0=cost)
     if not good or cnt < MIN_MATCHES:
         return start
-    R, t, lam, steps, costs = R0, t0, LAMBDA0, 0, [cost]
-    for _ in range(iters):
-        delta = cholesky_solve(A, lam, g)
-        if delta is None:
-            return start
-        Rc, tc = step(R, t, delta)
-        if np.array_equal(Rc, R) and np.array_equal(tc, t):
-            break                                          # the step moved nothing, and no later one will
-        A2, g2, c2, n2, w2, _ = evaluate(Rc, tc, xh, xh2, thr, ok)
-        if c2 < cost * (1.0 - ACCEPT_REL):
-            R, t, A, g, cost, cnt, w = Rc, tc, A2, g2, c2, n2, w2
-            lam = max(lam / 10.0, LAMBDA_MIN)
-            steps += 1
-            costs.append(cost)
-        else:
-            lam *= 10.0
+
+    def propose(pose, delta):
+        Rc, tc = step(*pose, delta)
+        return None if np.array_equal(Rc, pose[0]) and np.array_equal(tc, pose[1]) else (Rc, tc)
+
+    def evaluate_pose(pose):                               # one pass: the cost of the candidate and, if it is kept, its equations
+        A2, g2, c2, n2, w2, _ = evaluate(*pose, xh, xh2, thr, ok)
+        return c2, n2, w2, (A2, g2)
+
+    out = schedule((R0, t0), cost, cnt, w, iters, lambda pose, eqs: eqs, propose, evaluate_pose, (A, g))
+    if out is None:
+        return start
+    (R, t), cost, cnt, w, steps, costs = out
     return dict(R=R, t=t, mask=w, cost=cost, count=cnt, steps=steps, costs=costs, cost0=costs[0])
 
 

@@ -11,7 +11,6 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,6 +18,7 @@ import torch
 
 from roma_amd import _lib
 from tests import depth_warp_ref as D
+from tests.helpers import kernel_resources
 
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -187,21 +187,7 @@ def test_wrappers_refuse_cpu_tensors_smooth_mask_and_unknown_modes():
 def test_depth_warp_kernels_use_no_scratch_and_spill_nothing():
     """The compiler's resource report of csrc/depth_warp.hip (the recipe of test_triangulate.py); LDS holds the pair constants and,
     in the metrics kernel, one partial per wave."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    assert os.path.exists(hipcc), f"{hipcc} is missing: the resource report needs the compiler"
-    src = os.path.join(ROOT, "roma_amd", "csrc", "depth_warp.hip")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        mm = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if mm:
-            cur = kernels.setdefault(mm.group(1), {})
-            continue
-        mm = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\d+)", line)
-        if mm and cur is not None:
-            cur[mm.group(1).strip()] = int(mm.group(2))
+    kernels = kernel_resources("depth_warp.hip")
     assert sum("warp_kpts_kernel" in k for k in kernels) == 3 and sum("dense_metrics_kernel" in k for k in kernels) == 3, sorted(kernels)
     assert sum("dense_metrics_finish_kernel" in k for k in kernels) == 1 and len(kernels) == 7, sorted(kernels)
     for name, k in kernels.items():

@@ -32,7 +32,9 @@ def _worker(rank, world, port, npairs, q, wire=None):
         lo, hi = shard_range(npairs, world, rank)
         warp, cert = match_sharded(_fake_match, list(range(npairs)), wire_dtype=wire)
         if rank == 0:
-            q.put((warp.clone(), cert.clone(), (lo, hi)))
+            # as numpy arrays, pickled by value: a tensor goes through the queue as a file descriptor that the parent has to fetch
+            # from this process, which may have exited by then (ConnectionResetError in q.get)
+            q.put((warp.numpy(), cert.numpy(), (lo, hi)))
         else:
             assert warp is None and cert is None
             q.put((None, None, (lo, hi)))
@@ -54,7 +56,7 @@ def test_two_rank_shard_and_gather(npairs):
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
-    warp, cert, _ = next(r for r in results if r[0] is not None)
+    warp, cert = (torch.from_numpy(a) for a in next(r for r in results if r[0] is not None)[:2])
     assert warp.shape == (npairs, 3, 4, 4) and cert.shape == (npairs, 3, 4)
     for i in range(npairs):
         assert float(warp[i].min()) == float(warp[i].max()) == float(i)
@@ -77,7 +79,7 @@ def test_two_rank_gather_with_fp16_wire_format():
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
-    warp, cert, _ = next(r for r in results if r[0] is not None)
+    warp, cert = (torch.from_numpy(a) for a in next(r for r in results if r[0] is not None)[:2])
     assert warp.dtype == torch.float32 and cert.dtype == torch.float32 and warp.shape == (npairs, 3, 4, 4)
     for i in range(npairs):
         assert float(warp[i].min()) == float(warp[i].max()) == float(i)

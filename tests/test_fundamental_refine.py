@@ -10,10 +10,6 @@ scenes 11-14 (MEASURED_*, on an MI355X) times 10 — the margin is for another s
 whatever is measured: 1e-9 for |F_dev - F_np|_F (unit-norm models) and 1e-10 for the relative cost.  Measured: 1.51e-16 in the
 model, 3.49e-16 relative in the final cost, 1.30e-10 thr^2 in any match's r^2 (an outlier's), the same kept steps (6 / 7 / 3 / 4),
 inlier counts and masks on all four scenes; bounds: 1.51e-15, 3.49e-15, 1.30e-9 thr^2."""
-import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,9 +19,9 @@ from roma_amd import _lib
 from tests import fundamental_refine_ref as FR
 from tests import geometry_ref as G
 from tests import pose_ref as PR
+from tests.helpers import check_refine_entry_point_validates_arguments, dev, kernel_resources, to_np
 
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THR = 1.5
 SAMPLES = 300
 SCENES = list(range(100, 120))
@@ -128,25 +124,14 @@ def test_refinement_improves_the_mean_accuracy_over_20_scenes():
 
 
 def test_refine_fundamental_entry_point_validates_arguments_without_a_gpu():
-    lib = _lib.load()
-    buf = (ctypes.c_double * 32)()
-    a = ctypes.cast(buf, ctypes.c_void_p)
+    def bind(lib, a):
+        def call(xa=a, xb=a, F_in=a, out=a, steps=a, P=1, N=100, thr=1.5, iters=15):
+            return lib.roma_refine_fundamental(xa, xb, F_in, None, P, N, thr, iters, out, a, a, a, steps, None)
+        return call
 
-    def call(xa=a, xb=a, F_in=a, out=a, steps=a, P=1, N=100, thr=1.5, iters=15):
-        return lib.roma_refine_fundamental(xa, xb, F_in, None, P, N, thr, iters, out, a, a, a, steps, None)
-
-    assert call(xa=None) == _lib.ROMA_E_ARG and b"roma_refine_fundamental: null pointer" in lib.roma_last_error()
-    for kw in ("xb", "F_in", "out", "steps"):
-        assert call(**{kw: None}) == _lib.ROMA_E_ARG and b"null pointer" in lib.roma_last_error()
-    assert call(P=0) == _lib.ROMA_E_SHAPE and b"bad shape" in lib.roma_last_error()
-    assert call(N=7) == _lib.ROMA_E_SHAPE and b"need at least 8" in lib.roma_last_error()
-    for thr in (0.0, -1.0, float("nan")):
-        assert call(thr=thr) == _lib.ROMA_E_ARG and b"threshold" in lib.roma_last_error()
-    assert call(iters=-1) == _lib.ROMA_E_ARG and b"iters" in lib.roma_last_error()
-    odd = ctypes.c_void_p(ctypes.addressof(buf) + 8)
-    assert call(xa=odd) == _lib.ROMA_E_ALIGN and b"16-byte" in lib.roma_last_error()
-    assert call(xb=odd) == _lib.ROMA_E_ALIGN and b"16-byte" in lib.roma_last_error()
-    assert lib.roma_abi_version() == 5
+    check_refine_entry_point_validates_arguments("roma_refine_fundamental", bind, 8, null=("xa", "xb", "F_in", "out", "steps"),
+                                                 misaligned=("xa", "xb"))
+    assert _lib.load().roma_abi_version() == 5
 
 
 def test_new_entry_points_refuse_cpu_tensors_and_bad_counts():
@@ -168,21 +153,7 @@ def test_new_entry_points_refuse_cpu_tensors_and_bad_counts():
 
 def test_fundamental_refine_kernel_uses_no_scratch_and_spills_nothing():
     """The compiler's resource report of csrc/fundamental_refine.hip (the recipe of test_pose_refine.py)."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    assert os.path.exists(hipcc), f"{hipcc} is missing: the resource report needs the compiler"
-    src = os.path.join(ROOT, "roma_amd", "csrc", "fundamental_refine.hip")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    kernels = kernel_resources("fundamental_refine.hip")
     assert any("refine_fundamental_kernel" in k for k in kernels), sorted(kernels)
     for name, k in kernels.items():
         print(name, k)
@@ -190,14 +161,6 @@ def test_fundamental_refine_kernel_uses_no_scratch_and_spills_nothing():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _np(*ts):
-    return [t.cpu().numpy() for t in ts]
-
-
 def _assert_never_worse(F0, F, xa, xb, mask=None, thr=THR):
     """the truncated cost of the returned model, recomputed in numpy fp64, is not above that of the given one"""
     c0, c1 = FR.truncated_cost(F0, xa, xb, thr, mask), FR.truncated_cost(F, xa, xb, thr, mask)
@@ -231,10 +194,10 @@ def test_refine_parity_with_the_restatement():
     figs, checks = [], []
     for seed in (11, 12, 13, 14):
         xa, xb = G.two_view_scene(seed)[:2]
-        F0, _ = geometry.find_fundamental(_dev(xa), _dev(xb), threshold=THR, max_iters=SAMPLES, seed=seed)
-        F, mask, info = geometry.refine_fundamental(F0, _dev(xa), _dev(xb), THR, return_info=True)
+        F0, _ = geometry.find_fundamental(dev(xa), dev(xb), threshold=THR, max_iters=SAMPLES, seed=seed)
+        F, mask, info = geometry.refine_fundamental(F0, dev(xa), dev(xb), THR, return_info=True)
         assert F.shape == (3, 3) and F.dtype == torch.float64 and mask.shape == (5000,) and mask.dtype == torch.bool
-        F0, F, mask = _np(F0, F, mask)
+        F0, F, mask = to_np(F0, F, mask)
         o = FR.refine(F0, xa, xb, THR)
         _assert_output(F0, F, mask, info, xa, xb)
         r2d, r2n = FR.residuals(F, xa, xb) ** 2, FR.residuals(o["F"], xa, xb) ** 2
@@ -259,36 +222,36 @@ def test_refine_parity_with_the_restatement():
 def test_refine_determinism_and_batch_independence():
     from roma_amd import geometry
     xa, xb = _batch(20)
-    F0, _ = geometry.find_fundamental(_dev(xa), _dev(xb), threshold=THR, max_iters=SAMPLES, seed=5)
-    o1 = geometry.refine_fundamental(F0, _dev(xa), _dev(xb), THR, return_info=True)
-    o2 = geometry.refine_fundamental(F0, _dev(xa), _dev(xb), THR, return_info=True)
+    F0, _ = geometry.find_fundamental(dev(xa), dev(xb), threshold=THR, max_iters=SAMPLES, seed=5)
+    o1 = geometry.refine_fundamental(F0, dev(xa), dev(xb), THR, return_info=True)
+    o2 = geometry.refine_fundamental(F0, dev(xa), dev(xb), THR, return_info=True)
     assert o1[0].shape == (8, 3, 3) and o1[1].shape == (8, 2000) and o1[2]["steps"].shape == (8,)
     assert all(torch.equal(a, b) for a, b in zip(o1[:2], o2[:2])) and all(torch.equal(o1[2][k], o2[2][k]) for k in o1[2])
     assert int(o1[2]["steps"].max()) >= 1
     for i in range(8):
-        _assert_output(*_np(F0[i], o1[0][i], o1[1][i]), _info(o1[2], i), xa[i], xb[i])
+        _assert_output(*to_np(F0[i], o1[0][i], o1[1][i]), _info(o1[2], i), xa[i], xb[i])
         # pair i alone
-        s = geometry.refine_fundamental(F0[i], _dev(xa[i]), _dev(xb[i]), THR, return_info=True)
+        s = geometry.refine_fundamental(F0[i], dev(xa[i]), dev(xb[i]), THR, return_info=True)
         assert all(torch.equal(a, b[i]) for a, b in zip(s[:2], o1[:2])) and all(torch.equal(s[2][k], o1[2][k][i]) for k in s[2])
     # a refined model given back comes out bit for bit, with 0 steps
-    o3 = geometry.refine_fundamental(o1[0], _dev(xa), _dev(xb), THR, return_info=True)
+    o3 = geometry.refine_fundamental(o1[0], dev(xa), dev(xb), THR, return_info=True)
     assert torch.equal(o3[0], o1[0]) and torch.equal(o3[1], o1[1]) and int(o3[2]["steps"].max()) == 0
     assert torch.equal(o3[2]["cost"], o1[2]["cost"]) and torch.equal(o3[2]["count"], o1[2]["count"])
     # iters = 0 is the identity, with the model's own mask and cost
-    o4 = geometry.refine_fundamental(F0, _dev(xa), _dev(xb), THR, iters=0, return_info=True)
+    o4 = geometry.refine_fundamental(F0, dev(xa), dev(xb), THR, iters=0, return_info=True)
     assert torch.equal(o4[0], F0) and int(o4[2]["steps"].max()) == 0 and torch.equal(o4[2]["count"], o4[1].sum(-1).int())
     # the mask restricts the matches that carry weight: the same as handing over those matches alone
     only = torch.zeros(8, 2000, dtype=torch.bool, device=DEV)
     only[:, :1000] = True
-    Fm, mm, im = geometry.refine_fundamental(F0, _dev(xa), _dev(xb), THR, mask=only, return_info=True)
+    Fm, mm, im = geometry.refine_fundamental(F0, dev(xa), dev(xb), THR, mask=only, return_info=True)
     assert not bool(mm[:, 1000:].any()) and int(mm.sum()) > 0
-    Fh, mh = geometry.refine_fundamental(F0, _dev(xa[:, :1000]), _dev(xb[:, :1000]), THR)
+    Fh, mh = geometry.refine_fundamental(F0, dev(xa[:, :1000]), dev(xb[:, :1000]), THR)
     assert torch.equal(Fm, Fh) and torch.equal(mm[:, :1000], mh)
     for i in range(8):
-        _assert_output(*_np(F0[i], Fm[i], mm[i]), _info(im, i), xa[i], xb[i], mask_in=only[i].cpu().numpy())
+        _assert_output(*to_np(F0[i], Fm[i], mm[i]), _info(im, i), xa[i], xb[i], mask_in=only[i].cpu().numpy())
     # fp32 points are the same points in fp64
-    F32, m32 = geometry.refine_fundamental(F0, _dev(xa).float(), _dev(xb).float(), THR)
-    F64, m64 = geometry.refine_fundamental(F0, _dev(xa).float().double(), _dev(xb).float().double(), THR)
+    F32, m32 = geometry.refine_fundamental(F0, dev(xa).float(), dev(xb).float(), THR)
+    F64, m64 = geometry.refine_fundamental(F0, dev(xa).float().double(), dev(xb).float().double(), THR)
     assert torch.equal(F32, F64) and torch.equal(m32, m64)
 
 
@@ -299,33 +262,33 @@ def test_refine_of_degenerate_input_returns_the_input():
     from roma_amd import geometry
     N = 500
     xa, xb = _batch(60, n=7, N=N)
-    F0, _ = geometry.find_fundamental(_dev(xa), _dev(xb), threshold=THR, max_iters=SAMPLES, seed=2)
+    F0, _ = geometry.find_fundamental(dev(xa), dev(xb), threshold=THR, max_iters=SAMPLES, seed=2)
     F0 = F0.clone()
     F0[1] = 0.0                                                                                     # a zero F
-    F0[2] = _dev(np.outer([1.0, 2.0, 3.0], [0.5, -1.0, 2.0]) / 10.0)                                # a rank-1 F
+    F0[2] = dev(np.outer([1.0, 2.0, 3.0], [0.5, -1.0, 2.0]) / 10.0)                                # a rank-1 F
     F0[3, 1, 1] = float("nan")                                                                      # an F that is not finite
     mask = torch.ones(7, N, dtype=torch.bool, device=DEV)
     mask[4, 7:] = False                                                                             # fewer than 8 matches
     xa[5], xb[5] = np.nan, np.nan                                                                   # no finite match
-    F, m, info = geometry.refine_fundamental(F0, _dev(xa), _dev(xb), THR, mask=mask, return_info=True)
+    F, m, info = geometry.refine_fundamental(F0, dev(xa), dev(xb), THR, mask=mask, return_info=True)
     for i in (1, 2, 3, 4, 5):
         assert F[i].cpu().numpy().tobytes() == F0[i].cpu().numpy().tobytes(), i
         assert int(info["steps"][i]) == 0 and int(info["count"][i]) == int(m[i].sum()), i
-        _assert_never_worse(*_np(F0[i], F[i]), xa[i], xb[i], mask[i].cpu().numpy())
+        _assert_never_worse(*to_np(F0[i], F[i]), xa[i], xb[i], mask[i].cpu().numpy())
     assert not bool(m[1].any()) and not bool(m[3].any()) and not bool(m[5].any()) and int(m[4].sum()) <= 7 and not bool(m[4, 7:].any())
     assert float(info["cost"][5]) == 0.0 and float(info["cost"][1]) == N * THR ** 2
     for i in (0, 6):
-        s = geometry.refine_fundamental(F0[i], _dev(xa[i]), _dev(xb[i]), THR, return_info=True)
+        s = geometry.refine_fundamental(F0[i], dev(xa[i]), dev(xb[i]), THR, return_info=True)
         assert torch.equal(s[0], F[i]) and torch.equal(s[1], m[i]) and all(torch.equal(s[2][k], info[k][i]) for k in s[2])
         assert int(info["steps"][i]) >= 1
-        _assert_output(*_np(F0[i], F[i], m[i]), _info(info, i), xa[i], xb[i])
+        _assert_output(*to_np(F0[i], F[i], m[i]), _info(info, i), xa[i], xb[i])
 
 
 @pytest.mark.gpu
 def test_refine_graph_capture_replays_the_eager_result():
     from roma_amd import geometry
     xa, xb = G.two_view_scene(30, N=3000)[:2]
-    xa, xb = _dev(xa), _dev(xb)
+    xa, xb = dev(xa), dev(xb)
     F0, _ = geometry.find_fundamental(xa, xb, threshold=THR, max_iters=SAMPLES, seed=11)
     eager = geometry.refine_fundamental(F0, xa, xb, THR, return_info=True)
     s = torch.cuda.Stream()
@@ -340,7 +303,7 @@ def test_refine_graph_capture_replays_the_eager_result():
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(out[:2], eager[:2])) and all(torch.equal(out[2][k], eager[2][k]) for k in out[2])
     assert int(out[2]["steps"]) >= 1
-    _assert_output(*_np(F0, out[0], out[1]), out[2], xa.cpu().numpy(), xb.cpu().numpy())
+    _assert_output(*to_np(F0, out[0], out[1]), out[2], xa.cpu().numpy(), xb.cpu().numpy())
 
 
 @pytest.mark.gpu
@@ -354,12 +317,12 @@ def test_refined_estimators_are_more_accurate_over_20_scenes():
         scene = G.two_view_scene(seed)
         xa, xb = scene[:2]
         _, R_true, t_true = PR.scene_pose(seed)
-        da, db = _dev(xa), _dev(xb)
+        da, db = dev(xa), dev(xb)
         F0, m0 = geometry.find_fundamental(da, db, threshold=THR, max_iters=SAMPLES, seed=seed)
         F1, m1 = geometry.find_fundamental(da, db, threshold=THR, max_iters=SAMPLES, seed=seed, refine_iters=15)
         Rp, tp, _ = geometry.estimate_pose_uncalibrated(da, db, K, K, THR, max_iters=SAMPLES, seed=seed)
         Rq, tq, _ = geometry.estimate_pose_uncalibrated(da, db, K, K, THR, max_iters=SAMPLES, seed=seed, refine_iters=15)
-        F0, F1, Rp, tp, Rq, tq = _np(F0, F1, Rp, tp, Rq, tq)
+        F0, F1, Rp, tp, Rq, tq = to_np(F0, F1, Rp, tp, Rq, tq)
         c0, c1 = _assert_never_worse(F0, F1, xa, xb)
         rows.append((_rms_clean(F0, scene), PR.rotation_error_deg(Rp, R_true), PR.translation_error_deg(tp, t_true),
                      _rms_clean(F1, scene), PR.rotation_error_deg(Rq, R_true), PR.translation_error_deg(tq, t_true)))
@@ -376,7 +339,7 @@ def test_refined_estimators_are_more_accurate_over_20_scenes():
 def test_refine_iters_zero_is_the_unchanged_default():
     from roma_amd import geometry
     xa, xb = _batch(80, n=3, N=1500)
-    da, db = _dev(xa).float(), _dev(xb).float()
+    da, db = dev(xa).float(), dev(xb).float()
     K = PR.K_SCENE
     a = geometry.find_fundamental(da, db, threshold=THR, max_iters=SAMPLES, seed=9)
     b = geometry.find_fundamental(da, db, threshold=THR, max_iters=SAMPLES, seed=9, refine_iters=0)
@@ -415,7 +378,7 @@ def test_refined_fundamental_integration_with_match_and_sample():
     assert F.shape == (2, 3, 3) and mask.shape == (2, 500) and mask.dtype == torch.bool and torch.isfinite(F).all()
     for i in range(2):
         xa, xb = kA[i].double().cpu().numpy(), kB[i].double().cpu().numpy()
-        c0, c1 = _assert_never_worse(*_np(F0[i], F[i]), xa, xb, thr=3.0)
+        c0, c1 = _assert_never_worse(*to_np(F0[i], F[i]), xa, xb, thr=3.0)
         sv = np.linalg.svd(F[i].cpu().numpy(), compute_uv=False)
         print(f"pair {i}: cost {c0:.4f} -> {c1:.4f}, sigma_3 / sigma_1 = {sv[2] / sv[0]:.2e}")
         assert sv[2] / sv[0] < 1e-12

@@ -49,6 +49,7 @@ from tests import pose_refine_ref as RR
 from tests import test_fundamental_refine as TF
 from tests import test_geometry as TG
 from tests import test_homography_refine as TH
+from tests.helpers import dev, to_np
 
 DEV = "cuda:0"
 KA, KB, THR_G = GS.K_A, GS.K_B, GS.THR_G
@@ -261,25 +262,17 @@ def test_restatements_meet_the_f_and_h_criteria():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _np(*ts):
-    return [t.cpu().numpy() for t in ts]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("motion", ["forward", "turn"])
 def test_calibration_and_five_point_models_match_numpy(motion):
     from roma_amd import geometry
     xa, xb = GS.general_scene(motion, 5, N=600)[:2]
-    r = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), "essential", THR_G, max_iters=200, seed=7, K_A=_dev(KA), K_B=_dev(KB))
+    r = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), "essential", THR_G, max_iters=200, seed=7, K_A=dev(KA), K_B=dev(KB))
     for got, K in ((r["T_A"], KA), (r["T_B"], KB)):
         want = np.linalg.inv(K)
         assert np.abs(got[0].cpu().numpy() - want).max() <= 1e-15 * np.abs(want).max(), (got, want)
     xh, xh2 = PR.calibrate(xa, KA), PR.calibrate(xb, KB)
-    models, valid, samples = _np(r["models"][0], r["valid"][0], r["samples"][0])
+    models, valid, samples = to_np(r["models"][0], r["valid"][0], r["samples"][0])
     assert models.shape == (200, 10, 3, 3) and np.array_equal(samples, PR.minimal_samples(xa[None], xb[None], 200, 7)[0])
     usable, skipped, checked, worst = 0, 0, 0, 0.0
     for h in range(200):
@@ -317,9 +310,9 @@ def test_essential_inlier_counts_equal_an_fp64_recount_on_calibrated_points():
     from roma_amd import geometry
     xa, xb = GS.general_scene("forward", 6)[:2]
     xa[17] = np.nan
-    r = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), "essential", THR_G, max_iters=100, seed=9, K_A=KA, K_B=KB)
+    r = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), "essential", THR_G, max_iters=100, seed=9, K_A=KA, K_B=KB)
     xh, xh2 = PR.calibrate(xa, KA), PR.calibrate(xb, KB)
-    models, valid, count = _np(r["models"][0], r["valid"][0], r["count"][0])
+    models, valid, count = to_np(r["models"][0], r["valid"][0], r["count"][0])
     assert valid.sum() > 200
     t2 = THR_G * THR_G
     for h, s in zip(*np.nonzero(valid)):
@@ -335,13 +328,13 @@ def test_essential_selection_and_local_optimisation():
     from roma_amd import geometry
     xa, xb = GS.general_scene("turn", 13)[:2]
     xh, xh2 = PR.calibrate(xa, KA), PR.calibrate(xb, KB)
-    r = geometry.score_hypotheses(_dev(xa), _dev(xb), "essential", THR_G, max_iters=500, seed=21, K_A=KA, K_B=KB)
+    r = geometry.score_hypotheses(dev(xa), dev(xb), "essential", THR_G, max_iters=500, seed=21, K_A=KA, K_B=KB)
     best = int(np.argmin(r["cost"][0].cpu().numpy().reshape(-1)))
     want = G.sign_fixed(r["models"][0].cpu().numpy().reshape(-1, 3, 3)[best])
-    E0, mask0 = geometry.find_essential(_dev(xa), _dev(xb), KA, KB, THR_G, max_iters=500, seed=21, lo_iters=0)
+    E0, mask0 = geometry.find_essential(dev(xa), dev(xb), KA, KB, THR_G, max_iters=500, seed=21, lo_iters=0)
     E0 = E0.cpu().numpy()
     assert np.abs(E0 - want).max() <= 1e-9, (E0, want)
-    E3, mask3 = geometry.find_essential(_dev(xa), _dev(xb), KA, KB, THR_G, max_iters=500, seed=21, lo_iters=3)
+    E3, mask3 = geometry.find_essential(dev(xa), dev(xb), KA, KB, THR_G, max_iters=500, seed=21, lo_iters=3)
     E3 = E3.cpu().numpy()
     t2 = THR_G * THR_G
     assert _msac(E3, xh, xh2, t2) < _msac(E0, xh, xh2, t2), (_msac(E3, xh, xh2, t2), _msac(E0, xh, xh2, t2))
@@ -360,11 +353,11 @@ def test_essential_selection_and_local_optimisation():
 def test_pose_of_every_motion(motion, seed):
     from roma_amd import geometry
     xa, xb, truth, R_true, t_true = GS.general_scene(motion, seed)
-    a, b = _dev(xa).float(), _dev(xb).float()
+    a, b = dev(xa).float(), dev(xb).float()
     E, emask = geometry.find_essential(a, b, KA, KB, THR_G, max_iters=500, seed=seed)
     R, t, mask = geometry.estimate_pose(a, b, KA, KB, THR_G, max_iters=500, seed=seed)
     assert R.shape == (3, 3) and R.dtype == torch.float64 and t.shape == (3,) and mask.shape == (2000,) and mask.dtype == torch.bool
-    _check_pose(R_true, t_true, *_np(emask, R, t, mask), truth, f"device, {motion} {seed}")
+    _check_pose(R_true, t_true, *to_np(emask, R, t, mask), truth, f"device, {motion} {seed}")
 
 
 @pytest.mark.gpu
@@ -385,7 +378,7 @@ def test_recover_pose_picks_the_true_candidate(sign, esign):
             assert np.isfinite(la).all() and np.isfinite(lb).all() and min(np.abs(la).min(), np.abs(lb).min()) > 1e-6
         Rw, tw, mw, cw = PR.recover_pose(E, xa, xb, KA, KB, truth)
         assert cw == truth.sum() and np.abs(Rw - R_true).max() < 1e-9 and np.abs(tw - t_true).max() < 1e-9
-        R, t, mask = geometry.recover_pose(_dev(E), _dev(xa), _dev(xb), KA, KB, _dev(truth))
+        R, t, mask = geometry.recover_pose(dev(E), dev(xa), dev(xb), KA, KB, dev(truth))
         assert np.abs(R.cpu().numpy() - R_true).max() < 1e-9 and np.abs(t.cpu().numpy() - t_true).max() < 1e-9, motion
         assert np.array_equal(mask.cpu().numpy(), mw) and int(mask.sum()) == cw, motion
 
@@ -395,12 +388,12 @@ def test_recover_pose_picks_the_true_candidate(sign, esign):
 def test_estimate_pose_uncalibrated_is_find_fundamental_then_recover_pose_of_kb_f_ka(motion):
     from roma_amd import geometry
     xa, xb, truth, R_true, t_true = GS.general_scene(motion, 0)
-    a, b, Ka, Kb = _dev(xa).float(), _dev(xb).float(), _dev(KA), _dev(KB)
+    a, b, Ka, Kb = dev(xa).float(), dev(xb).float(), dev(KA), dev(KB)
     R, t, mask = geometry.estimate_pose_uncalibrated(a, b, Ka, Kb, 1.5, max_iters=2000, seed=17)
     F, fmask = geometry.find_fundamental(a, b, threshold=1.5, max_iters=2000, seed=17)
     R2, t2, mask2 = geometry.recover_pose(Kb.transpose(-1, -2) @ F @ Ka, a, b, Ka, Kb, fmask)
     assert torch.equal(R, R2) and torch.equal(t, t2) and torch.equal(mask, mask2)
-    _check_pose(R_true, t_true, *_np(fmask, R, t, mask), truth, f"device F pose, {motion}", F_POSE_FACTOR)
+    _check_pose(R_true, t_true, *to_np(fmask, R, t, mask), truth, f"device F pose, {motion}", F_POSE_FACTOR)
 
 
 @pytest.mark.gpu
@@ -409,10 +402,10 @@ def test_refine_parity_with_the_restatement(motion):
     from roma_amd import geometry
     seed = 0
     xa, xb, truth, R_true, t_true = GS.general_scene(motion, seed)
-    R0, t0, _ = geometry.estimate_pose(_dev(xa), _dev(xb), KA, KB, THR_G, max_iters=500, seed=seed)
-    R, t, mask, info = geometry.refine_pose(R0, t0, _dev(xa), _dev(xb), KA, KB, THR_G, return_info=True)
+    R0, t0, _ = geometry.estimate_pose(dev(xa), dev(xb), KA, KB, THR_G, max_iters=500, seed=seed)
+    R, t, mask, info = geometry.refine_pose(R0, t0, dev(xa), dev(xb), KA, KB, THR_G, return_info=True)
     assert R.shape == (3, 3) and R.dtype == torch.float64 and t.shape == (3,) and mask.shape == (2000,) and mask.dtype == torch.bool
-    R0, t0, R, t, mask = _np(R0, t0, R, t, mask)
+    R0, t0, R, t, mask = to_np(R0, t0, R, t, mask)
     o = RR.refine(R0, t0, xa, xb, KA, KB, THR_G)
     c0, c1 = _cost(R0, t0, xa, xb, KA, KB, THR_G), _cost(R, t, xa, xb, KA, KB, THR_G)
     assert c1 <= c0, (c0, c1)
@@ -446,13 +439,13 @@ def test_estimate_relative_pose_with_two_cameras(motion):
     thr = RR.calibrated_threshold(1.5, cam0, cam1)
     assert abs(thr - THR_G) < 1e-18 and abs(thr - 1.5 / 805) > 1e-4 and abs(thr - 1.5 / 632.5) > 1e-4
     xa, xb, truth, R_true, t_true = GS.general_scene(motion, 0, KA=Ka, KB=Kb)
-    a, b = _dev(xa).float(), _dev(xb).float()
+    a, b = dev(xa).float(), dev(xb).float()
     pose, info = geometry.estimate_relative_pose(a, b, cam0, cam1, {"max_epipolar_error": 1.5, "max_iterations": 500}, seed=4)
     R0, t0, _ = geometry.estimate_pose(a, b, Ka, Kb, thr, max_iters=500, seed=4)
     R1, t1, mask1, info1 = geometry.refine_pose(R0, t0, a, b, Ka, Kb, thr, return_info=True)
     assert torch.equal(info["inliers"], mask1) and torch.equal(pose.R, R1) and torch.equal(pose.t, t1)
     assert int(info["num_inliers"]) == int(mask1.sum()) and torch.equal(info["model_score"], info1["cost"])
-    R0, t0, R, t, mask = _np(R0, t0, pose.R, pose.t, info["inliers"])
+    R0, t0, R, t, mask = to_np(R0, t0, pose.R, pose.t, info["inliers"])
     xa32, xb32 = xa.astype(np.float32).astype(np.float64), xb.astype(np.float32).astype(np.float64)
     c0, c1 = _cost(R0, t0, xa32, xb32, Ka, Kb, thr), _cost(R, t, xa32, xb32, Ka, Kb, thr)
     assert c1 <= c0, (c0, c1)
@@ -490,20 +483,20 @@ def _batch_scenes():
 def test_batch_with_intrinsics_of_its_own_per_pair():
     from roma_amd import geometry
     scenes, Kas, Kbs = _batch_scenes()
-    a, b = _dev(np.stack([s[0] for s in scenes])).float(), _dev(np.stack([s[1] for s in scenes])).float()
-    E, emask = geometry.find_essential(a, b, _dev(Kas), _dev(Kbs), THR_G, max_iters=500, seed=5)
-    R, t, mask = geometry.estimate_pose(a, b, _dev(Kas), _dev(Kbs), THR_G, max_iters=500, seed=5)
+    a, b = dev(np.stack([s[0] for s in scenes])).float(), dev(np.stack([s[1] for s in scenes])).float()
+    E, emask = geometry.find_essential(a, b, dev(Kas), dev(Kbs), THR_G, max_iters=500, seed=5)
+    R, t, mask = geometry.estimate_pose(a, b, dev(Kas), dev(Kbs), THR_G, max_iters=500, seed=5)
     assert R.shape == (6, 3, 3) and t.shape == (6, 3) and mask.shape == (6, 2000)
     for p, (motion, seed) in enumerate(BATCH):
-        _check_pose(scenes[p][3], scenes[p][4], *_np(emask[p], R[p], t[p], mask[p]), scenes[p][2], f"pair {p} ({motion} {seed})")
+        _check_pose(scenes[p][3], scenes[p][4], *to_np(emask[p], R[p], t[p], mask[p]), scenes[p][2], f"pair {p} ({motion} {seed})")
     # pair 0 alone, with its own cameras, is what it is in the batch (a later pair draws other samples: the draw counts pairs)
     E1, m1 = geometry.find_essential(a[0], b[0], Kas[0], Kbs[0], THR_G, max_iters=500, seed=5)
     assert torch.equal(E1, E[0]) and torch.equal(m1, emask[0])
-    R2, t2, mask2 = geometry.refine_pose(R, t, a, b, _dev(Kas), _dev(Kbs), THR_G)
+    R2, t2, mask2 = geometry.refine_pose(R, t, a, b, dev(Kas), dev(Kbs), THR_G)
     for p in range(6):
         xa32, xb32 = a[p].double().cpu().numpy(), b[p].double().cpu().numpy()
-        c0 = _cost(*_np(R[p], t[p]), xa32, xb32, Kas[p], Kbs[p], THR_G)
-        c1 = _cost(*_np(R2[p], t2[p]), xa32, xb32, Kas[p], Kbs[p], THR_G)
+        c0 = _cost(*to_np(R[p], t[p]), xa32, xb32, Kas[p], Kbs[p], THR_G)
+        c1 = _cost(*to_np(R2[p], t2[p]), xa32, xb32, Kas[p], Kbs[p], THR_G)
         assert c1 <= c0, (p, c0, c1)
         assert PR.rotation_error_deg(R2[p].cpu().numpy(), scenes[p][3]) <= ROT_BOUND_DEG
         assert PR.translation_error_deg(t2[p].cpu().numpy(), scenes[p][4]) <= TRANS_BOUND_DEG
@@ -513,10 +506,10 @@ def test_batch_with_intrinsics_of_its_own_per_pair():
 def test_three_chunks_return_what_one_chunk_returns(monkeypatch):
     from roma_amd import geometry
     scenes, Kas, Kbs = _batch_scenes()
-    a, b = _dev(np.stack([s[0] for s in scenes])).float(), _dev(np.stack([s[1] for s in scenes])).float()
+    a, b = dev(np.stack([s[0] for s in scenes])).float(), dev(np.stack([s[1] for s in scenes])).float()
     planar = [GS.general_planar_scene(s) for s in range(6)]
-    ha, hb = _dev(np.stack([s[0] for s in planar])), _dev(np.stack([s[1] for s in planar]))
-    Ka, Kb = _dev(Kas), _dev(Kbs)
+    ha, hb = dev(np.stack([s[0] for s in planar])), dev(np.stack([s[1] for s in planar]))
+    Ka, Kb = dev(Kas), dev(Kbs)
     calls = [(geometry.KIND_E, lambda: geometry.find_essential(a, b, Ka, Kb, THR_G, max_iters=500, seed=5)),
              (geometry.KIND_F, lambda: geometry.find_fundamental(a, b, threshold=1.5, max_iters=500, seed=5)),
              (geometry.KIND_H, lambda: geometry.find_homography(ha, hb, threshold=3.0, max_iters=500, seed=5))]
@@ -539,15 +532,15 @@ def test_a_singular_k_b_gives_the_identity_pose():
     from roma_amd import geometry
     eye, zero = torch.eye(3, dtype=torch.float64, device=DEV), torch.zeros(3, dtype=torch.float64, device=DEV)
     xa, xb = GS.general_scene("sideways", 3, N=500)[:2]
-    singular = _dev(KB).clone()
+    singular = dev(KB).clone()
     singular[1, 1] = 0.0
-    E, emask = geometry.find_essential(_dev(xa), _dev(xb), _dev(KA), singular, THR_G, max_iters=100, seed=0)
+    E, emask = geometry.find_essential(dev(xa), dev(xb), dev(KA), singular, THR_G, max_iters=100, seed=0)
     assert torch.equal(E, torch.zeros_like(E)) and not bool(emask.any())
-    R, t, mask = geometry.estimate_pose(_dev(xa), _dev(xb), _dev(KA), singular, THR_G, max_iters=100, seed=0)
+    R, t, mask = geometry.estimate_pose(dev(xa), dev(xb), dev(KA), singular, THR_G, max_iters=100, seed=0)
     assert torch.equal(R, eye) and torch.equal(t, zero) and not bool(mask.any())
-    r = geometry.score_hypotheses(_dev(xa), _dev(xb), "essential", THR_G, 100, 0, _dev(KA), singular)
+    r = geometry.score_hypotheses(dev(xa), dev(xb), "essential", THR_G, 100, 0, dev(KA), singular)
     assert not bool(r["valid"].any()) and bool((r["samples"] == -1).all())
-    E, emask = geometry.find_essential(_dev(xa), _dev(xb), _dev(KA), _dev(KB), THR_G, max_iters=100, seed=0)   # and the regular pair has one
+    E, emask = geometry.find_essential(dev(xa), dev(xb), dev(KA), dev(KB), THR_G, max_iters=100, seed=0)   # and the regular pair has one
     assert bool(E.any()) and int(emask.sum()) > 300
 
 
@@ -565,11 +558,11 @@ def test_minimal_f_and_h_models_match_numpy_with_unequal_images():
     """test_minimal_models_match_numpy_fp64 of tests/test_geometry.py on the forward scene and the planar one"""
     from roma_amd import geometry
     xa, xb = GS.general_scene("forward", 5, N=600)[:2]
-    r = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), "fundamental", 1.5, max_iters=400, seed=7)
+    r = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), "fundamental", 1.5, max_iters=400, seed=7)
     _assert_transforms(r, xa, xb)
-    TA, TB = _np(r["T_A"][0], r["T_B"][0])
+    TA, TB = to_np(r["T_A"][0], r["T_B"][0])
     xh, xh2 = TG._normalised(xa, xb, TA, TB)
-    models, valid, samples = _np(r["models"][0], r["valid"][0], r["samples"][0])
+    models, valid, samples = to_np(r["models"][0], r["valid"][0], r["samples"][0])
     checked = 0
     for h in range(400):
         if samples[h, 0] < 0:
@@ -587,11 +580,11 @@ def test_minimal_f_and_h_models_match_numpy_with_unequal_images():
                 checked += 1
     assert checked > 300
     xa, xb = GS.general_planar_scene(5, N=600)[:2]
-    rh = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), "homography", 3.0, max_iters=400, seed=8)
+    rh = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), "homography", 3.0, max_iters=400, seed=8)
     _assert_transforms(rh, xa, xb)
-    TA, TB = _np(rh["T_A"][0], rh["T_B"][0])
+    TA, TB = to_np(rh["T_A"][0], rh["T_B"][0])
     xh, xh2 = TG._normalised(xa, xb, TA, TB)
-    models, valid, samples = _np(rh["models"][0], rh["valid"][0], rh["samples"][0])
+    models, valid, samples = to_np(rh["models"][0], rh["valid"][0], rh["samples"][0])
     checked = 0
     for h in range(400):
         if samples[h, 0] < 0:
@@ -616,13 +609,13 @@ def test_f_and_h_selection_and_local_optimisation_with_unequal_images(model, thr
     from roma_amd import geometry
     xa, xb = (GS.general_scene("turn", 13) if model == "fundamental" else GS.general_planar_scene(13))[:2]
     fn = geometry.find_fundamental if model == "fundamental" else geometry.find_homography
-    r = geometry.score_hypotheses(_dev(xa), _dev(xb), model, thr, max_iters=500, seed=21)
+    r = geometry.score_hypotheses(dev(xa), dev(xb), model, thr, max_iters=500, seed=21)
     _assert_transforms(r, xa, xb)
     best = int(np.argmin(r["cost"][0].cpu().numpy().reshape(-1)))
     slot = r["models"][0].cpu().numpy().reshape(-1, 3, 3)[best]
     ok = G.usable(xa, xb)
     want = G.finish(model, G.denormalise(model, slot, G.transform(G.normalisation(xa, ok)), G.transform(G.normalisation(xb, ok))))
-    M0, mask0 = fn(_dev(xa), _dev(xb), threshold=thr, max_iters=500, seed=21, lo_iters=0)
+    M0, mask0 = fn(dev(xa), dev(xb), threshold=thr, max_iters=500, seed=21, lo_iters=0)
     M0 = M0.cpu().numpy()
     assert np.abs(M0 - want).max() <= 1e-9 * np.abs(want).max(), (M0, want)
     t2 = thr * thr
@@ -630,7 +623,7 @@ def test_f_and_h_selection_and_local_optimisation_with_unequal_images(model, thr
     def msac(M):
         e = G.errors(model, M, xa, xb)
         return np.where(e < t2, e, t2).sum()
-    M3, _ = fn(_dev(xa), _dev(xb), threshold=thr, max_iters=500, seed=21, lo_iters=3)
+    M3, _ = fn(dev(xa), dev(xb), threshold=thr, max_iters=500, seed=21, lo_iters=3)
     assert msac(M3.cpu().numpy()) < msac(M0), (msac(M3.cpu().numpy()), msac(M0))
 
 
@@ -640,7 +633,7 @@ def test_fundamental_of_two_cameras(motion):
     from roma_amd import geometry
     xa, xb, truth = GS.general_scene(motion, 0)[:3]
     ca, cb = GS.general_scene(motion, 0, sigma=0.0)[:2]
-    M, mask = geometry.find_fundamental(_dev(xa).float(), _dev(xb).float(), threshold=1.5, max_iters=500, seed=1)
+    M, mask = geometry.find_fundamental(dev(xa).float(), dev(xb).float(), threshold=1.5, max_iters=500, seed=1)
     assert M.shape == (3, 3) and M.dtype == torch.float64 and mask.shape == (2000,) and mask.dtype == torch.bool
     TG._check_two_view(M.cpu().numpy(), mask.cpu().numpy(), truth, ca, cb)
 
@@ -649,7 +642,7 @@ def test_fundamental_of_two_cameras(motion):
 def test_homography_between_unequal_images():
     from roma_amd import geometry
     xa, xb, truth, H = GS.general_planar_scene(0)
-    M, mask = geometry.find_homography(_dev(xa), _dev(xb), threshold=3.0, max_iters=500, seed=2)
+    M, mask = geometry.find_homography(dev(xa), dev(xb), threshold=3.0, max_iters=500, seed=2)
     assert M.shape == (3, 3) and M.dtype == torch.float64 and float(M[2, 2]) == 1.0
     TG._check_planar(M.cpu().numpy(), mask.cpu().numpy(), truth, H)
 
@@ -662,9 +655,9 @@ def test_fundamental_refine_parity_with_unequal_images(motion):
     from roma_amd import geometry
     bound_model, bound_cost = (TF.PARITY_MODEL, TF.PARITY_COST_REL) if motion == "turn" else (10 * REF_F_MODEL, 10 * REF_F_COST_REL)
     xa, xb = GS.general_scene(motion, 0)[:2]
-    F0, _ = geometry.find_fundamental(_dev(xa), _dev(xb), threshold=TF.THR, max_iters=TF.SAMPLES, seed=0)
-    F, mask, info = geometry.refine_fundamental(F0, _dev(xa), _dev(xb), TF.THR, return_info=True)
-    F0, F, mask = _np(F0, F, mask)
+    F0, _ = geometry.find_fundamental(dev(xa), dev(xb), threshold=TF.THR, max_iters=TF.SAMPLES, seed=0)
+    F, mask, info = geometry.refine_fundamental(F0, dev(xa), dev(xb), TF.THR, return_info=True)
+    F0, F, mask = to_np(F0, F, mask)
     o = FR.refine(F0, xa, xb, TF.THR)
     TF._assert_output(F0, F, mask, info, xa, xb)
     r2d, r2n = FR.residuals(F, xa, xb) ** 2, FR.residuals(o["F"], xa, xb) ** 2
@@ -683,9 +676,9 @@ def test_homography_refine_parity_with_unequal_images():
     """one case of test_refine_parity_with_the_restatement of tests/test_homography_refine.py, its bounds as they stand"""
     from roma_amd import geometry
     xa, xb = GS.general_planar_scene(0)[:2]
-    H0, _ = geometry.find_homography(_dev(xa), _dev(xb), threshold=TH.THR, max_iters=TH.SAMPLES, seed=0)
-    H, mask, info = geometry.refine_homography(H0, _dev(xa), _dev(xb), TH.THR, return_info=True)
-    H0, H, mask = _np(H0, H, mask)
+    H0, _ = geometry.find_homography(dev(xa), dev(xb), threshold=TH.THR, max_iters=TH.SAMPLES, seed=0)
+    H, mask, info = geometry.refine_homography(H0, dev(xa), dev(xb), TH.THR, return_info=True)
+    H0, H, mask = to_np(H0, H, mask)
     o = HR.refine(H0, xa, xb, TH.THR)
     TH._assert_output(H0, H, mask, info, xa, xb)
     ed, en = (HR.residuals(H, xa, xb) ** 2).sum(-1), (HR.residuals(o["H"], xa, xb) ** 2).sum(-1)

@@ -8,6 +8,7 @@ import torch
 
 from roma_amd import _lib
 from tests import geometry_ref as G
+from tests.helpers import dev
 
 DEV = "cuda:0"
 
@@ -133,10 +134,6 @@ def _check_planar(M, mask, truth, H):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("N", [7, 8, 5000])
 def test_sample_indices_equal_the_restatement(N):
@@ -145,11 +142,11 @@ def test_sample_indices_equal_the_restatement(N):
     xa, xb = rng.uniform(0, 1000, (3, N, 2)), rng.uniform(0, 1000, (3, N, 2))
     for model in ("fundamental", "homography"):
         for seed in (0, 123456789):
-            got = geometry.minimal_samples(_dev(xa), _dev(xb), model, max_iters=300, seed=seed).cpu().numpy()
+            got = geometry.minimal_samples(dev(xa), dev(xb), model, max_iters=300, seed=seed).cpu().numpy()
             want = G.minimal_samples(xa, xb, model, 300, seed)
             assert np.array_equal(got, want), (model, seed)
     if N == 7:                                             # every valid F sample is a permutation of the 7: redraws were needed
-        got = geometry.minimal_samples(_dev(xa), _dev(xb), "fundamental", max_iters=300, seed=0).cpu().numpy().reshape(-1, 7)
+        got = geometry.minimal_samples(dev(xa), dev(xb), "fundamental", max_iters=300, seed=0).cpu().numpy().reshape(-1, 7)
         assert (got[:, 0] >= 0).mean() > 0.85 and all(sorted(r) == list(range(7)) for r in got if r[0] >= 0)
 
 
@@ -163,7 +160,7 @@ def _normalised(xa, xb, TA, TB):
 def test_minimal_models_match_numpy_fp64():
     from roma_amd import geometry
     xa, xb, _, _, _, _ = G.two_view_scene(5, N=600, outlier_frac=0.3)
-    r = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), "fundamental", 1.5, max_iters=400, seed=7)
+    r = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), "fundamental", 1.5, max_iters=400, seed=7)
     TA, TB = r["T_A"][0].cpu().numpy(), r["T_B"][0].cpu().numpy()
     xh, xh2 = _normalised(xa, xb, TA, TB)
     models, valid, samples = r["models"][0].cpu().numpy(), r["valid"][0].cpu().numpy(), r["samples"][0].cpu().numpy()
@@ -183,7 +180,7 @@ def test_minimal_models_match_numpy_fp64():
                 assert d < 1e-6, (h, r_, d)
                 checked += 1
     assert checked > 300
-    rh = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), "homography", 3.0, max_iters=400, seed=8)
+    rh = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), "homography", 3.0, max_iters=400, seed=8)
     TA, TB = rh["T_A"][0].cpu().numpy(), rh["T_B"][0].cpu().numpy()
     xh, xh2 = _normalised(xa, xb, TA, TB)
     models, valid, samples = rh["models"][0].cpu().numpy(), rh["valid"][0].cpu().numpy(), rh["samples"][0].cpu().numpy()
@@ -213,7 +210,7 @@ def test_inlier_counts_equal_an_fp64_recount(model, thr):
     else:
         xa, xb = G.planar_scene(6, N=3000)[:2]
     xa[17] = np.nan                                       # a non-finite match: never an inlier
-    r = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), model, thr, max_iters=200, seed=9)
+    r = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), model, thr, max_iters=200, seed=9)
     TA, TB = r["T_A"][0].cpu().numpy(), r["T_B"][0].cpu().numpy()
     models, valid, count = r["models"][0].cpu().numpy(), r["valid"][0].cpu().numpy(), r["count"][0].cpu().numpy()
     assert valid.sum() > 100
@@ -233,11 +230,11 @@ def test_selection_and_local_optimisation(model, thr, iters):
     from roma_amd import geometry
     xa, xb = (G.two_view_scene(13) if model == "fundamental" else G.planar_scene(13))[:2]
     fn = geometry.find_fundamental if model == "fundamental" else geometry.find_homography
-    r = geometry.score_hypotheses(_dev(xa), _dev(xb), model, thr, max_iters=iters, seed=21)
+    r = geometry.score_hypotheses(dev(xa), dev(xb), model, thr, max_iters=iters, seed=21)
     best = int(np.argmin(r["cost"][0].cpu().numpy().reshape(-1)))
     slot = r["models"][0].cpu().numpy().reshape(-1, 3, 3)[best]
     want = G.finish(model, G.denormalise(model, slot, r["T_A"][0].cpu().numpy(), r["T_B"][0].cpu().numpy()))
-    M0, mask0 = fn(_dev(xa), _dev(xb), threshold=thr, max_iters=iters, seed=21, lo_iters=0)
+    M0, mask0 = fn(dev(xa), dev(xb), threshold=thr, max_iters=iters, seed=21, lo_iters=0)
     M0 = M0.cpu().numpy()
     assert np.abs(M0 - want).max() <= 1e-9 * np.abs(want).max(), (M0, want)
     t2 = thr * thr
@@ -245,7 +242,7 @@ def test_selection_and_local_optimisation(model, thr, iters):
     def msac(M):
         e = G.errors(model, M, xa, xb)
         return np.where(e < t2, e, t2).sum()
-    M3, _ = fn(_dev(xa), _dev(xb), threshold=thr, max_iters=iters, seed=21, lo_iters=3)
+    M3, _ = fn(dev(xa), dev(xb), threshold=thr, max_iters=iters, seed=21, lo_iters=3)
     assert msac(M3.cpu().numpy()) < msac(M0), (msac(M3.cpu().numpy()), msac(M0))
 
 
@@ -271,7 +268,7 @@ def test_megadepth_batch_fits_in_256_mb():
 def test_two_view_scene():
     from roma_amd import geometry
     xa, xb, truth, F, ca, cb = G.two_view_scene(11)
-    M, mask = geometry.find_fundamental(_dev(xa).float(), _dev(xb).float(), threshold=1.5, seed=1)
+    M, mask = geometry.find_fundamental(dev(xa).float(), dev(xb).float(), threshold=1.5, seed=1)
     assert M.shape == (3, 3) and M.dtype == torch.float64 and mask.shape == (5000,) and mask.dtype == torch.bool
     _check_two_view(M.cpu().numpy(), mask.cpu().numpy(), truth, ca, cb)
 
@@ -280,7 +277,7 @@ def test_two_view_scene():
 def test_planar_scene():
     from roma_amd import geometry
     xa, xb, truth, H = G.planar_scene(12)
-    M, mask = geometry.find_homography(_dev(xa), _dev(xb), threshold=3.0, seed=2)
+    M, mask = geometry.find_homography(dev(xa), dev(xb), threshold=3.0, seed=2)
     assert M.shape == (3, 3) and M.dtype == torch.float64 and float(M[2, 2]) == 1.0
     _check_planar(M.cpu().numpy(), mask.cpu().numpy(), truth, H)
 
@@ -289,8 +286,8 @@ def test_planar_scene():
 def test_determinism_and_batch_independence():
     from roma_amd import geometry
     scenes = [G.two_view_scene(20 + i, N=2000) for i in range(8)]
-    xa = _dev(np.stack([s[0] for s in scenes])).float()
-    xb = _dev(np.stack([s[1] for s in scenes])).float()
+    xa = dev(np.stack([s[0] for s in scenes])).float()
+    xb = dev(np.stack([s[1] for s in scenes])).float()
     M1, m1 = geometry.find_fundamental(xa, xb, threshold=1.5, max_iters=3000, seed=5)
     M2, m2 = geometry.find_fundamental(xa, xb, threshold=1.5, max_iters=3000, seed=5)
     assert torch.equal(M1, M2) and torch.equal(m1, m2)
@@ -298,7 +295,7 @@ def test_determinism_and_batch_independence():
     xa2, xb2 = xa.clone(), xb.clone()
     for i in range(8):
         if i != 3:
-            xa2[i], xb2[i] = _dev(other[i][0]).float(), _dev(other[i][1]).float()
+            xa2[i], xb2[i] = dev(other[i][0]).float(), dev(other[i][1]).float()
     M3, m3 = geometry.find_fundamental(xa2, xb2, threshold=1.5, max_iters=3000, seed=5)
     assert torch.equal(M3[3], M1[3]) and torch.equal(m3[3], m1[3])
     H1, h1 = geometry.find_homography(xa, xb, max_iters=500, seed=6)
@@ -337,7 +334,7 @@ def test_argument_errors():
 def test_graph_capture_replays_the_eager_result():
     from roma_amd import geometry
     xa, xb = G.two_view_scene(30, N=3000)[:2]
-    xa, xb = _dev(xa).float(), _dev(xb).float()
+    xa, xb = dev(xa).float(), dev(xb).float()
     eager = geometry.find_fundamental(xa, xb, threshold=1.5, max_iters=2000, seed=11)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())

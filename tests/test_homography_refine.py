@@ -11,10 +11,6 @@ hard ceilings that hold whatever is measured: 1e-9 for |H_dev - H_np|_F / |H_np|
 the F refinement.  Measured: 1.77e-15 in the model, 1.28e-15 relative in the final cost, 5.18e-10 thr^2 in any match's e (an
 outlier's), the same kept steps (3 / 6 / 6 / 4), inlier counts and masks on all four scenes; bounds: 1.77e-14, 1.28e-14, 5.18e-9
 thr^2."""
-import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,9 +19,9 @@ import torch
 from roma_amd import _lib
 from tests import geometry_ref as G
 from tests import homography_refine_ref as HR
+from tests.helpers import check_refine_entry_point_validates_arguments, dev, kernel_resources, to_np
 
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THR = 1.5
 SAMPLES = 300
 SCENES = list(range(100, 120))
@@ -114,25 +110,14 @@ def test_refinement_improves_the_mean_accuracy_over_20_scenes():
 
 
 def test_refine_homography_entry_point_validates_arguments_without_a_gpu():
-    lib = _lib.load()
-    buf = (ctypes.c_double * 32)()
-    a = ctypes.cast(buf, ctypes.c_void_p)
+    def bind(lib, a):
+        def call(xa=a, xb=a, H_in=a, out=a, steps=a, P=1, N=100, thr=1.5, iters=15):
+            return lib.roma_refine_homography(xa, xb, H_in, None, P, N, thr, iters, out, a, a, a, steps, None)
+        return call
 
-    def call(xa=a, xb=a, H_in=a, out=a, steps=a, P=1, N=100, thr=1.5, iters=15):
-        return lib.roma_refine_homography(xa, xb, H_in, None, P, N, thr, iters, out, a, a, a, steps, None)
-
-    assert call(xa=None) == _lib.ROMA_E_ARG and b"roma_refine_homography: null pointer" in lib.roma_last_error()
-    for kw in ("xb", "H_in", "out", "steps"):
-        assert call(**{kw: None}) == _lib.ROMA_E_ARG and b"null pointer" in lib.roma_last_error()
-    assert call(P=0) == _lib.ROMA_E_SHAPE and b"bad shape" in lib.roma_last_error()
-    assert call(N=3) == _lib.ROMA_E_SHAPE and b"need at least 4" in lib.roma_last_error()
-    for thr in (0.0, -1.0, float("nan")):
-        assert call(thr=thr) == _lib.ROMA_E_ARG and b"threshold" in lib.roma_last_error()
-    assert call(iters=-1) == _lib.ROMA_E_ARG and b"iters" in lib.roma_last_error()
-    odd = ctypes.c_void_p(ctypes.addressof(buf) + 8)
-    assert call(xa=odd) == _lib.ROMA_E_ALIGN and b"16-byte" in lib.roma_last_error()
-    assert call(xb=odd) == _lib.ROMA_E_ALIGN and b"16-byte" in lib.roma_last_error()
-    assert lib.roma_abi_version() == 5
+    check_refine_entry_point_validates_arguments("roma_refine_homography", bind, 4, null=("xa", "xb", "H_in", "out", "steps"),
+                                                 misaligned=("xa", "xb"))
+    assert _lib.load().roma_abi_version() == 5
 
 
 def test_new_entry_points_refuse_cpu_tensors_and_bad_counts():
@@ -151,21 +136,7 @@ def test_new_entry_points_refuse_cpu_tensors_and_bad_counts():
 
 def test_homography_refine_kernel_uses_no_scratch_and_spills_nothing():
     """The compiler's resource report of csrc/homography_refine.hip (the recipe of test_fundamental_refine.py)."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    assert os.path.exists(hipcc), f"{hipcc} is missing: the resource report needs the compiler"
-    src = os.path.join(ROOT, "roma_amd", "csrc", "homography_refine.hip")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    kernels = kernel_resources("homography_refine.hip")
     assert any("refine_homography_kernel" in k for k in kernels), sorted(kernels)
     for name, k in kernels.items():
         print(name, k)
@@ -173,14 +144,6 @@ def test_homography_refine_kernel_uses_no_scratch_and_spills_nothing():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _np(*ts):
-    return [t.cpu().numpy() for t in ts]
-
-
 def _assert_never_worse(H0, H, xa, xb, mask=None, thr=THR):
     """the truncated cost of the returned model, recomputed in numpy fp64, is not above that of the given one"""
     c0, c1 = HR.truncated_cost(H0, xa, xb, thr, mask), HR.truncated_cost(H, xa, xb, thr, mask)
@@ -218,10 +181,10 @@ def test_refine_parity_with_the_restatement():
     figs, checks = [], []
     for seed in (11, 12, 13, 14):
         xa, xb = G.planar_scene(seed)[:2]
-        H0, _ = geometry.find_homography(_dev(xa), _dev(xb), threshold=THR, max_iters=SAMPLES, seed=seed)
-        H, mask, info = geometry.refine_homography(H0, _dev(xa), _dev(xb), THR, return_info=True)
+        H0, _ = geometry.find_homography(dev(xa), dev(xb), threshold=THR, max_iters=SAMPLES, seed=seed)
+        H, mask, info = geometry.refine_homography(H0, dev(xa), dev(xb), THR, return_info=True)
         assert H.shape == (3, 3) and H.dtype == torch.float64 and mask.shape == (5000,) and mask.dtype == torch.bool
-        H0, H, mask = _np(H0, H, mask)
+        H0, H, mask = to_np(H0, H, mask)
         o = HR.refine(H0, xa, xb, THR)
         _assert_output(H0, H, mask, info, xa, xb)
         ed, en = (HR.residuals(H, xa, xb) ** 2).sum(-1), (HR.residuals(o["H"], xa, xb) ** 2).sum(-1)
@@ -251,13 +214,13 @@ def test_refine_small_and_awkward_shapes(N, P):
     nothing to refine), 100 is fewer matches than threads, 257 and 1000 leave a tail."""
     from roma_amd import geometry
     xa, xb, H_true = _batch(40, n=P, N=N, **({"outlier_frac": 0.0} if N == 4 else {}))
-    da, db = _dev(xa), _dev(xb)
-    H0 = _dev(H_true) if N == 4 else geometry.find_homography(da, db, threshold=THR, max_iters=SAMPLES, seed=3)[0]
+    da, db = dev(xa), dev(xb)
+    H0 = dev(H_true) if N == 4 else geometry.find_homography(da, db, threshold=THR, max_iters=SAMPLES, seed=3)[0]
     H, mask, info = geometry.refine_homography(H0, da, db, THR, return_info=True)
     assert H.shape == (P, 3, 3) and mask.shape == (P, N) and mask.dtype == torch.bool and info["steps"].shape == (P,)
     assert torch.equal(info["count"], mask.sum(-1).int())
     for i in range(P):
-        _assert_output(*_np(H0[i], H[i], mask[i]), _info(info, i), xa[i], xb[i])
+        _assert_output(*to_np(H0[i], H[i], mask[i]), _info(info, i), xa[i], xb[i])
     print(f"N = {N}, P = {P}: kept steps {info['steps'].tolist()}, inliers {info['count'].tolist()}")
     assert int(info["steps"].max()) >= 1
 
@@ -266,7 +229,7 @@ def test_refine_small_and_awkward_shapes(N, P):
 def test_refine_determinism_and_batch_independence():
     from roma_amd import geometry
     xa, xb, _ = _batch(20)
-    da, db = _dev(xa), _dev(xb)
+    da, db = dev(xa), dev(xb)
     H0, _ = geometry.find_homography(da, db, threshold=THR, max_iters=SAMPLES, seed=5)
     o1 = geometry.refine_homography(H0, da, db, THR, return_info=True)
     o2 = geometry.refine_homography(H0, da, db, THR, return_info=True)
@@ -274,7 +237,7 @@ def test_refine_determinism_and_batch_independence():
     assert _same(o1, o2)
     assert int(o1[2]["steps"].max()) >= 1
     for i in range(8):
-        _assert_output(*_np(H0[i], o1[0][i], o1[1][i]), _info(o1[2], i), xa[i], xb[i])
+        _assert_output(*to_np(H0[i], o1[0][i], o1[1][i]), _info(o1[2], i), xa[i], xb[i])
         # pair i alone
         s = geometry.refine_homography(H0[i], da[i], db[i], THR, return_info=True)
         assert all(torch.equal(a, b[i]) for a, b in zip(s[:2], o1[:2])) and all(torch.equal(s[2][k], o1[2][k][i]) for k in s[2])
@@ -293,7 +256,7 @@ def test_refine_determinism_and_batch_independence():
     Hh, mh = geometry.refine_homography(H0, da[:, :1000], db[:, :1000], THR)
     assert torch.equal(Hm, Hh) and torch.equal(mm[:, :1000], mh)
     for i in range(8):
-        _assert_output(*_np(H0[i], Hm[i], mm[i]), _info(im, i), xa[i], xb[i], mask_in=only[i].cpu().numpy())
+        _assert_output(*to_np(H0[i], Hm[i], mm[i]), _info(im, i), xa[i], xb[i], mask_in=only[i].cpu().numpy())
     # fp32 points are the same points in fp64
     H32, m32 = geometry.refine_homography(H0, da.float(), db.float(), THR)
     H64, m64 = geometry.refine_homography(H0, da.float().double(), db.float().double(), THR)
@@ -307,38 +270,38 @@ def test_refine_of_degenerate_input_returns_the_input():
     from roma_amd import geometry
     N = 500
     xa, xb, _ = _batch(60, n=7, N=N)
-    H0, _ = geometry.find_homography(_dev(xa), _dev(xb), threshold=THR, max_iters=SAMPLES, seed=2)
+    H0, _ = geometry.find_homography(dev(xa), dev(xb), threshold=THR, max_iters=SAMPLES, seed=2)
     H0 = H0.clone()
     H0[1] = 0.0                                                                                     # a zero H
-    H0[2, 2] = _dev(np.array([1.0 / 512.0, 0.0, -1.0]))                                             # w = x / 512 - 1: zero at x = 512
+    H0[2, 2] = dev(np.array([1.0 / 512.0, 0.0, -1.0]))                                             # w = x / 512 - 1: zero at x = 512
     H0[3, 1, 1] = float("nan")                                                                      # an H that is not finite
     mask = torch.ones(7, N, dtype=torch.bool, device=DEV)
     mask[4, 3:] = False                                                                             # fewer than 4 matches
     xa[5], xb[5] = np.nan, np.nan                                                                   # no finite match
-    H, m, info = geometry.refine_homography(H0, _dev(xa), _dev(xb), THR, mask=mask, return_info=True)
+    H, m, info = geometry.refine_homography(H0, dev(xa), dev(xb), THR, mask=mask, return_info=True)
     for i in (1, 3, 4, 5):
         assert H[i].cpu().numpy().tobytes() == H0[i].cpu().numpy().tobytes(), i
         assert int(info["steps"][i]) == 0 and int(info["count"][i]) == int(m[i].sum()), i
-        _assert_never_worse(*_np(H0[i], H[i]), xa[i], xb[i], mask[i].cpu().numpy())
+        _assert_never_worse(*to_np(H0[i], H[i]), xa[i], xb[i], mask[i].cpu().numpy())
     assert not bool(m[1].any()) and not bool(m[3].any()) and not bool(m[5].any()) and int(m[4].sum()) <= 3 and not bool(m[4, 3:].any())
     assert float(info["cost"][5]) == 0.0 and float(info["cost"][1]) == N * THR ** 2
     w = xa[2, :, 0] / 512.0 - 1.0
     assert (w < 0).any() and (w > 0).any()
-    _assert_output(*_np(H0[2], H[2], m[2]), _info(info, 2), xa[2], xb[2])
+    _assert_output(*to_np(H0[2], H[2], m[2]), _info(info, 2), xa[2], xb[2])
     assert torch.isfinite(H[2]).all() and torch.isfinite(info["cost"][2])
     for i in (0, 2, 6):
-        s = geometry.refine_homography(H0[i], _dev(xa[i]), _dev(xb[i]), THR, return_info=True)
+        s = geometry.refine_homography(H0[i], dev(xa[i]), dev(xb[i]), THR, return_info=True)
         assert torch.equal(s[0], H[i]) and torch.equal(s[1], m[i]) and all(torch.equal(s[2][k], info[k][i]) for k in s[2])
     for i in (0, 6):
         assert int(info["steps"][i]) >= 1
-        _assert_output(*_np(H0[i], H[i], m[i]), _info(info, i), xa[i], xb[i])
+        _assert_output(*to_np(H0[i], H[i], m[i]), _info(info, i), xa[i], xb[i])
 
 
 @pytest.mark.gpu
 def test_refine_graph_capture_replays_the_eager_result():
     from roma_amd import geometry
     xa, xb = G.planar_scene(30, N=3000)[:2]
-    xa, xb = _dev(xa), _dev(xb)
+    xa, xb = dev(xa), dev(xb)
     H0, _ = geometry.find_homography(xa, xb, threshold=THR, max_iters=SAMPLES, seed=11)
     eager = geometry.refine_homography(H0, xa, xb, THR, return_info=True)
     s = torch.cuda.Stream()
@@ -353,14 +316,14 @@ def test_refine_graph_capture_replays_the_eager_result():
     torch.cuda.synchronize()
     assert _same(out, eager)
     assert int(out[2]["steps"]) >= 1
-    _assert_output(*_np(H0, out[0], out[1]), out[2], xa.cpu().numpy(), xb.cpu().numpy())
+    _assert_output(*to_np(H0, out[0], out[1]), out[2], xa.cpu().numpy(), xb.cpu().numpy())
 
 
 @pytest.mark.gpu
 def test_refine_iters_zero_is_the_unchanged_default():
     from roma_amd import geometry
     xa, xb, _ = _batch(80, n=3, N=1500)
-    da, db = _dev(xa).float(), _dev(xb).float()
+    da, db = dev(xa).float(), dev(xb).float()
     a = geometry.find_homography(da, db, threshold=THR, max_iters=SAMPLES, seed=9)
     b = geometry.find_homography(da, db, threshold=THR, max_iters=SAMPLES, seed=9, refine_iters=0)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
@@ -378,10 +341,10 @@ def test_refined_find_homography_is_more_accurate_over_20_scenes():
     rows = []
     for seed in SCENES:
         xa, xb, _, H_true = G.planar_scene(seed)
-        da, db = _dev(xa), _dev(xb)
+        da, db = dev(xa), dev(xb)
         H0, _ = geometry.find_homography(da, db, threshold=THR, max_iters=SAMPLES, seed=seed)
         H1, _ = geometry.find_homography(da, db, threshold=THR, max_iters=SAMPLES, seed=seed, refine_iters=15)
-        H0, H1 = _np(H0, H1)
+        H0, H1 = to_np(H0, H1)
         c0, c1 = _assert_never_worse(H0, H1, xa, xb)
         rows.append((G.corner_error(H0, H_true), G.corner_error(H1, H_true)))
         print(f"scene {seed}: find_homography corner error {rows[-1][0]:.4f} px, refine_iters=15 {rows[-1][1]:.4f} px, "
@@ -397,9 +360,9 @@ def test_homography_corner_error_is_the_benchmark_metric():
     from roma_amd import geometry
     W, Hh = G.W_IMG, G.H_IMG
     xa, xb, H_true = _batch(90, n=4, N=1000)
-    H_est, _ = geometry.find_homography(_dev(xa), _dev(xb), threshold=THR, max_iters=SAMPLES, seed=1)
+    H_est, _ = geometry.find_homography(dev(xa), dev(xb), threshold=THR, max_iters=SAMPLES, seed=1)
     scale = min(W, Hh) / 480.0
-    got = geometry.homography_corner_error(H_est, _dev(H_true), W, Hh, scale)
+    got = geometry.homography_corner_error(H_est, dev(H_true), W, Hh, scale)
     assert got.shape == (4,) and got.dtype == torch.float64
     want = np.array([HR.corner_error_hpatches(e, t, W, Hh, scale) for e, t in zip(H_est.cpu().numpy(), H_true)])
     print(f"corner errors {got.tolist()} px, restatement {want.tolist()}")
@@ -408,7 +371,7 @@ def test_homography_corner_error_is_the_benchmark_metric():
     assert one.shape == () and abs(float(one) - HR.corner_error_hpatches(H_est[0].cpu().numpy(), H_true[0], W, Hh)) < 1e-9
     zero = H_est.clone()
     zero[2] = 0.0                                                                      # find_homography's "no model"
-    z = geometry.homography_corner_error(zero, _dev(H_true), W, Hh, scale)
+    z = geometry.homography_corner_error(zero, dev(H_true), W, Hh, scale)
     assert torch.isinf(z[2]) and z[2] > 0 and torch.equal(z[[0, 1, 3]], got[[0, 1, 3]])
 
 
@@ -437,5 +400,5 @@ def test_refined_homography_integration_with_match_and_sample():
     assert H.shape == (2, 3, 3) and mask.shape == (2, 500) and mask.dtype == torch.bool and torch.isfinite(H).all()
     for i in range(2):
         xa, xb = kA[i].double().cpu().numpy(), kB[i].double().cpu().numpy()
-        c0, c1 = _assert_never_worse(*_np(H0[i], H[i]), xa, xb, thr=3.0)
+        c0, c1 = _assert_never_worse(*to_np(H0[i], H[i]), xa, xb, thr=3.0)
         print(f"pair {i}: cost {c0:.4f} -> {c1:.4f}, {int(m0[i].sum())} -> {int(mask[i].sum())} inliers")

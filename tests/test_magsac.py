@@ -8,7 +8,6 @@ import ctypes
 import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ from roma_amd import _lib
 from tests import geometry_ref as G
 from tests import magsac_ref as MR
 from tests import pose_ref as PR
+from tests.helpers import dev, kernel_resources
 
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,29 +123,10 @@ def test_restatement_meets_the_accuracy_criteria(row):
     _wins(row, results)
 
 
-def _resource_report(src):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    assert os.path.exists(hipcc), f"{hipcc} is missing: the resource report needs the compiler"
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return kernels
-
-
 def test_magsac_instantiations_use_no_scratch_and_spill_nothing():
     """The compiler's resource report of the MAGSAC++ instantiations (last template argument 1): no scratch, no spills, and the scoring
     kernel — its loss nodes in LDS beside the points — keeps the occupancy of its MSAC counterpart."""
-    g = _resource_report(os.path.join(ROOT, "roma_amd", "csrc", "geometry.hip"))
-    e = _resource_report(os.path.join(ROOT, "roma_amd", "csrc", "essential.hip"))
+    g, e = kernel_resources("geometry.hip"), kernel_resources("essential.hip")
 
     def one(kernels, pattern):
         hit = [k for k in kernels if re.search(pattern, k)]
@@ -164,10 +145,6 @@ def test_magsac_instantiations_use_no_scratch_and_spill_nothing():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 def _scene(row, seed, N):
     return (G.planar_scene(seed, N=N) if row == "H" else G.two_view_scene(seed, N=N))[:2]
 
@@ -177,7 +154,7 @@ _K_DEV = []
 
 def _Kd():
     if not _K_DEV:                                            # once: no copy from the host inside a graph capture
-        _K_DEV.append(_dev(K))
+        _K_DEV.append(dev(K))
     return _K_DEV[0]
 
 
@@ -213,7 +190,7 @@ def test_slot_costs_equal_an_fp64_recount(row, N):
     xa, xb = _scene(row, 6, N)
     bad = 17 if N > 17 else 3
     xa[bad] = np.nan                                          # a non-finite match: L = 1, never an inlier
-    r = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), MODEL[row], thr, max_iters=200, seed=9, scoring="magsac", **_kw(row))
+    r = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), MODEL[row], thr, max_iters=200, seed=9, scoring="magsac", **_kw(row))
     valid, count, cost = r["valid"][0].cpu().numpy(), r["count"][0].cpu().numpy(), r["cost"][0].cpu().numpy()
     assert valid.sum() > 100
     t2 = thr * thr
@@ -228,7 +205,7 @@ def test_slot_costs_equal_an_fp64_recount(row, N):
     assert ((lo_c <= cost[valid]) & (cost[valid] <= hi_c)).all()
     assert (count[~valid] == 0).all() and np.isinf(cost[~valid]).all()
     if N == 3000:                                             # the costs differ from the MSAC costs of the same slots
-        r0 = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), MODEL[row], thr, max_iters=200, seed=9, **_kw(row))
+        r0 = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), MODEL[row], thr, max_iters=200, seed=9, **_kw(row))
         assert torch.equal(r0["count"], r["count"]) and torch.equal(r0["models"], r["models"])
         assert not torch.equal(r0["cost"], r["cost"])
 
@@ -242,7 +219,7 @@ def test_selection_and_reweighted_local_optimisation(row):
     from roma_amd import geometry
     thr, iters, _ = MR.CASES[row]
     xa, xb = _scene(row, 13, 2000)
-    r = geometry.score_hypotheses(_dev(xa), _dev(xb), MODEL[row], thr, max_iters=iters, seed=21, scoring="magsac", **_kw(row))
+    r = geometry.score_hypotheses(dev(xa), dev(xb), MODEL[row], thr, max_iters=iters, seed=21, scoring="magsac", **_kw(row))
     best = int(np.argmin(r["cost"][0].cpu().numpy().reshape(-1)))
     slot = r["models"][0].cpu().numpy().reshape(-1, 3, 3)[best]
     t2 = thr * thr
@@ -262,8 +239,8 @@ def test_selection_and_reweighted_local_optimisation(row):
 
         def cost64(M):
             return MR.cost(G.errors(MODEL[row], M, xa, xb), t2)
-    M0, _ = _find(row, _dev(xa), _dev(xb), thr, iters, 21, lo_iters=0, scoring="magsac")
-    M3, mask3 = _find(row, _dev(xa), _dev(xb), thr, iters, 21, lo_iters=3, scoring="magsac")
+    M0, _ = _find(row, dev(xa), dev(xb), thr, iters, 21, lo_iters=0, scoring="magsac")
+    M3, mask3 = _find(row, dev(xa), dev(xb), thr, iters, 21, lo_iters=3, scoring="magsac")
     M0, M3 = M0.cpu().numpy(), M3.cpu().numpy()
     assert np.abs(M0 - want).max() <= 1e-9 * np.abs(want).max(), (M0, want)
     print(f"{row}: MAGSAC++ cost of the best slot {cost64(M0):.6f}, after 3 rounds {cost64(M3):.6f}, restatement {cost64(ref):.6f}")
@@ -284,7 +261,7 @@ def test_selection_and_reweighted_local_optimisation(row):
 
 def _batch(row, seeds, N=2000):
     scenes = [_scene(row, s, N) for s in seeds]
-    return _dev(np.stack([s[0] for s in scenes])), _dev(np.stack([s[1] for s in scenes]))
+    return dev(np.stack([s[0] for s in scenes])), dev(np.stack([s[1] for s in scenes]))
 
 
 @pytest.mark.gpu
@@ -310,7 +287,7 @@ def test_device_meets_the_accuracy_criteria(row):
         xa, xb, truth = MR.case_scene(row, scene)
         results[scene] = {}
         for scoring in ("msac", "magsac"):
-            M, mask = _find(row, _dev(xa), _dev(xb), thr, iters, seed, scoring=scoring)
+            M, mask = _find(row, dev(xa), dev(xb), thr, iters, seed, scoring=scoring)
             results[scene][scoring] = MR.criteria(row, M.cpu().numpy(), mask.cpu().numpy(), xa, xb, truth)
     _wins(row, results)
 
@@ -371,7 +348,7 @@ def test_magsac_degenerate_input_gives_a_zero_model():
 def test_magsac_graph_capture_replays_the_eager_result(row):
     thr, iters, _ = MR.CASES[row]
     xa, xb = _scene(row, 30, 2000)
-    xa, xb = _dev(xa).float(), _dev(xb).float()
+    xa, xb = dev(xa).float(), dev(xb).float()
     eager = _find(row, xa, xb, thr, iters, 11, scoring="magsac")
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -393,7 +370,7 @@ def test_pose_entry_points_pass_the_scoring_on():
     find_fundamental with that scoring (refine_iters and refine_pose compose unchanged behind it)."""
     from roma_amd import geometry
     xa, xb = G.two_view_scene(13, N=2000)[:2]
-    xa, xb, k = _dev(xa), _dev(xb), _Kd()
+    xa, xb, k = dev(xa), dev(xb), _Kd()
     thr = MR.CASES["E"][0]
     E, emask = geometry.find_essential(xa, xb, k, k, thr, max_iters=200, seed=3, scoring="magsac")
     want = geometry.recover_pose(E, xa, xb, k, k, emask)

@@ -2,9 +2,6 @@
 tests/pose_ref.py.  CPU tests pin the restatement to ground truth, the C-ABI argument checks and the kernels' resource report; GPU
 tests pin the kernels."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,9 +10,9 @@ import torch
 from roma_amd import _lib
 from tests import geometry_ref as G
 from tests import pose_ref as PR
+from tests.helpers import dev, kernel_resources
 
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THR = 1.5 / 800                                              # 1.5 px at the scenes' focal length
 ROT_BOUND_DEG, TRANS_BOUND_DEG = 0.1, 1.0                    # 5 x the worst error of the truth-aware fit over 8 scenes, rounded
 
@@ -146,21 +143,7 @@ def test_pose_functions_refuse_cpu_tensors_and_too_few_matches():
 def test_new_kernels_use_no_scratch_and_spill_nothing():
     """The compiler's resource report of csrc/essential.hip (what tools/kres.sh wraps): the 5-point solver is spread over 32 lanes
     so that no kernel needs scratch memory or spills a register."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    assert os.path.exists(hipcc), f"{hipcc} is missing: the resource report needs the compiler"
-    src = os.path.join(ROOT, "roma_amd", "csrc", "essential.hip")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    kernels = kernel_resources("essential.hip")
     for want in ("calibrate_kernel", "five_point_kernel", "essential_select_kernel", "recover_pose_kernel", "score_kernel",
                  "reduce_kernel"):
         assert any(want in k for k in kernels), (want, sorted(kernels))
@@ -170,12 +153,8 @@ def test_new_kernels_use_no_scratch_and_spill_nothing():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 def _K():
-    return _dev(PR.K_SCENE)
+    return dev(PR.K_SCENE)
 
 
 @pytest.mark.gpu
@@ -187,7 +166,7 @@ def test_essential_sample_indices_equal_the_restatement(N):
     if N == 5000:
         xa[1, 17] = np.nan                                # a non-finite match is never drawn
     for seed in (0, 123456789):
-        got = geometry.minimal_samples(_dev(xa), _dev(xb), "essential", max_iters=300, seed=seed, K_A=_K(), K_B=_K()).cpu().numpy()
+        got = geometry.minimal_samples(dev(xa), dev(xb), "essential", max_iters=300, seed=seed, K_A=_K(), K_B=_K()).cpu().numpy()
         want = PR.minimal_samples(xa, xb, 300, seed)
         assert got.shape == (3, 300, 5) and np.array_equal(got, want), seed
     if N == 5:
@@ -201,7 +180,7 @@ def test_essential_sample_indices_equal_the_restatement(N):
 def test_five_point_models_match_numpy_fp64():
     from roma_amd import geometry
     xa, xb = G.two_view_scene(5, N=600, outlier_frac=0.3)[:2]
-    r = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), "essential", THR, max_iters=400, seed=7, K_A=_K(), K_B=_K())
+    r = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), "essential", THR, max_iters=400, seed=7, K_A=_K(), K_B=_K())
     assert np.abs(r["T_A"][0].cpu().numpy() - np.linalg.inv(PR.K_SCENE)).max() < 1e-15
     xh, xh2 = PR.calibrate(xa, PR.K_SCENE), PR.calibrate(xb, PR.K_SCENE)
     models, valid, samples = r["models"][0].cpu().numpy(), r["valid"][0].cpu().numpy(), r["samples"][0].cpu().numpy()
@@ -242,7 +221,7 @@ def test_essential_inlier_counts_equal_an_fp64_recount():
     from roma_amd import geometry
     xa, xb = G.two_view_scene(6, N=3000)[:2]
     xa[17] = np.nan
-    r = geometry.score_hypotheses(_dev(xa[None]), _dev(xb[None]), "essential", THR, max_iters=100, seed=9, K_A=_K(), K_B=_K())
+    r = geometry.score_hypotheses(dev(xa[None]), dev(xb[None]), "essential", THR, max_iters=100, seed=9, K_A=_K(), K_B=_K())
     xh, xh2 = PR.calibrate(xa, PR.K_SCENE), PR.calibrate(xb, PR.K_SCENE)
     models, valid, count = r["models"][0].cpu().numpy(), r["valid"][0].cpu().numpy(), r["count"][0].cpu().numpy()
     assert valid.sum() > 200
@@ -261,13 +240,13 @@ def test_essential_selection_and_local_optimisation():
     from roma_amd import geometry
     xa, xb = G.two_view_scene(13)[:2]
     xh, xh2 = PR.calibrate(xa, PR.K_SCENE), PR.calibrate(xb, PR.K_SCENE)
-    r = geometry.score_hypotheses(_dev(xa), _dev(xb), "essential", THR, max_iters=500, seed=21, K_A=_K(), K_B=_K())
+    r = geometry.score_hypotheses(dev(xa), dev(xb), "essential", THR, max_iters=500, seed=21, K_A=_K(), K_B=_K())
     best = int(np.argmin(r["cost"][0].cpu().numpy().reshape(-1)))
     want = G.sign_fixed(r["models"][0].cpu().numpy().reshape(-1, 3, 3)[best])
-    E0, mask0 = geometry.find_essential(_dev(xa), _dev(xb), _K(), _K(), THR, max_iters=500, seed=21, lo_iters=0)
+    E0, mask0 = geometry.find_essential(dev(xa), dev(xb), _K(), _K(), THR, max_iters=500, seed=21, lo_iters=0)
     E0 = E0.cpu().numpy()
     assert np.abs(E0 - want).max() <= 1e-9, (E0, want)
-    E3, mask3 = geometry.find_essential(_dev(xa), _dev(xb), _K(), _K(), THR, max_iters=500, seed=21, lo_iters=3)
+    E3, mask3 = geometry.find_essential(dev(xa), dev(xb), _K(), _K(), THR, max_iters=500, seed=21, lo_iters=3)
     E3 = E3.cpu().numpy()
     t2 = THR * THR
     assert _msac(E3, xh, xh2, t2) < _msac(E0, xh, xh2, t2), (_msac(E3, xh, xh2, t2), _msac(E0, xh, xh2, t2))
@@ -286,8 +265,8 @@ def test_pose_scene(seed):
     from roma_amd import geometry
     xa, xb, truth = G.two_view_scene(seed)[:3]
     K = PR.K_SCENE
-    E, emask = geometry.find_essential(_dev(xa).float(), _dev(xb).float(), K, K, THR, seed=seed)
-    out = geometry.estimate_pose(_dev(xa).float(), _dev(xb).float(), K, K, THR, seed=seed)
+    E, emask = geometry.find_essential(dev(xa).float(), dev(xb).float(), K, K, THR, seed=seed)
+    out = geometry.estimate_pose(dev(xa).float(), dev(xb).float(), K, K, THR, seed=seed)
     R, t, mask = out
     assert R.shape == (3, 3) and R.dtype == torch.float64 and t.shape == (3,) and mask.shape == (5000,) and mask.dtype == torch.bool
     _print_truth_aware(seed, xa, xb, truth)
@@ -327,12 +306,12 @@ def test_recover_pose_picks_the_true_candidate(sign, esign):
             assert np.isfinite(la).all() and np.isfinite(lb).all() and min(np.abs(la).min(), np.abs(lb).min()) > 1e-6
         Rw, tw, mw, cw = PR.recover_pose(E, xa, xb, K, K, truth)
         assert cw == truth.sum() and np.abs(Rw - R_true).max() < 1e-9 and np.abs(tw - t_true).max() < 1e-9
-        R, t, mask = geometry.recover_pose(_dev(E), _dev(xa), _dev(xb), K, K, _dev(truth))
+        R, t, mask = geometry.recover_pose(dev(E), dev(xa), dev(xb), K, K, dev(truth))
         assert np.abs(R.cpu().numpy() - R_true).max() < 1e-9 and np.abs(t.cpu().numpy() - t_true).max() < 1e-9
         assert np.array_equal(mask.cpu().numpy(), mw) and int(mask.sum()) == cw
         # without a mask every match votes: the outliers' votes are whatever their depths say, the same on both sides
         Rw, tw, mw, cw = PR.recover_pose(E, xa, xb, K, K)
-        R, t, mask = geometry.recover_pose(_dev(E), _dev(xa), _dev(xb), _K(), _K())
+        R, t, mask = geometry.recover_pose(dev(E), dev(xa), dev(xb), _K(), _K())
         assert np.abs(R.cpu().numpy() - Rw).max() < 1e-9 and np.abs(t.cpu().numpy() - tw).max() < 1e-9
         assert (mask.cpu().numpy() != mw).sum() <= 2 and abs(int(mask.sum()) - cw) <= 2       # outliers may sit at a zero depth
 
@@ -341,8 +320,8 @@ def test_recover_pose_picks_the_true_candidate(sign, esign):
 def test_pose_determinism_and_batch_independence():
     from roma_amd import geometry
     scenes = [G.two_view_scene(20 + i, N=2000) for i in range(8)]
-    xa = _dev(np.stack([s[0] for s in scenes])).float()
-    xb = _dev(np.stack([s[1] for s in scenes])).float()
+    xa = dev(np.stack([s[0] for s in scenes])).float()
+    xb = dev(np.stack([s[1] for s in scenes])).float()
     K = _K()
     o1 = geometry.estimate_pose(xa, xb, K, K, THR, max_iters=500, seed=5)
     o2 = geometry.estimate_pose(xa, xb, K, K, THR, max_iters=500, seed=5)
@@ -353,7 +332,7 @@ def test_pose_determinism_and_batch_independence():
     xa2, xb2 = xa.clone(), xb.clone()
     for i in range(8):
         if i != 3:
-            xa2[i], xb2[i] = _dev(other[i][0]).float(), _dev(other[i][1]).float()
+            xa2[i], xb2[i] = dev(other[i][0]).float(), dev(other[i][1]).float()
     Ks = K.expand(8, 3, 3).clone()
     Ks[5, 0, 0] = 700.0                                   # per-pair intrinsics: another pair's K does not matter either
     E3, m3 = geometry.find_essential(xa2, xb2, Ks, Ks, THR, max_iters=500, seed=5)
@@ -375,13 +354,13 @@ def test_pose_of_degenerate_input_is_the_identity():
     singular[1, 1] = 0.0
     cases = [(torch.full((500, 2), 123.5, device=DEV), torch.full((500, 2), 123.5, device=DEV), K),
              (torch.full((500, 2), float("nan"), device=DEV), torch.full((500, 2), float("nan"), device=DEV), K),
-             (_dev(xa), _dev(xb), singular)]
+             (dev(xa), dev(xb), singular)]
     for a, b, k in cases:
         E, emask = geometry.find_essential(a, b, k, K, THR, max_iters=100, seed=0)
         assert torch.equal(E, torch.zeros_like(E)) and not bool(emask.any())
         R, t, mask = geometry.estimate_pose(a, b, k, K, THR, max_iters=100, seed=0)
         assert torch.equal(R, eye) and torch.equal(t, zero) and not bool(mask.any())
-    r = geometry.score_hypotheses(_dev(xa), _dev(xb), "essential", THR, 100, 0, singular, K)
+    r = geometry.score_hypotheses(dev(xa), dev(xb), "essential", THR, 100, 0, singular, K)
     assert not bool(r["valid"].any()) and bool((r["samples"] == -1).all())
 
 
@@ -389,7 +368,7 @@ def test_pose_of_degenerate_input_is_the_identity():
 def test_pose_graph_capture_replays_the_eager_result():
     from roma_amd import geometry
     xa, xb = G.two_view_scene(30, N=3000)[:2]
-    xa, xb, K = _dev(xa).float(), _dev(xb).float(), _K()
+    xa, xb, K = dev(xa).float(), dev(xb).float(), _K()
     eager = geometry.estimate_pose(xa, xb, K, K, THR, max_iters=500, seed=11)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -409,7 +388,7 @@ def test_pose_graph_capture_replays_the_eager_result():
 def test_estimate_pose_uncalibrated_is_find_fundamental_then_recover_pose():
     from roma_amd import geometry
     xa, xb = G.two_view_scene(31, N=3000)[:2]
-    xa, xb, K = _dev(xa).float(), _dev(xb).float(), _K()
+    xa, xb, K = dev(xa).float(), dev(xb).float(), _K()
     R, t, mask = geometry.estimate_pose_uncalibrated(xa, xb, K, K, 1.5, max_iters=2000, seed=17)
     F, fmask = geometry.find_fundamental(xa, xb, threshold=1.5, max_iters=2000, seed=17)
     R2, t2, mask2 = geometry.recover_pose(K.transpose(-1, -2) @ F @ K, xa, xb, K, K, fmask)

@@ -8,22 +8,17 @@ whose r^2 crosses thr^2 on one side only changes the weights.  So the bounds are
 over scenes 11-14 (MEASURED_*, on an MI355X) times 10.  Measured: 6.8e-15 deg in R, 4.3e-14 deg in t, 4.3e-16 relative in the final
 cost, 1.27e-10 thr^2 in any match's r^2 (an outlier's), the same kept steps, inlier counts and masks on all four scenes; bounds:
 6.8e-14 deg, 4.3e-13 deg, 4.3e-15, 1.27e-9 thr^2.  No match crossed thr^2 on one side only in these runs."""
-import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from roma_amd import _lib
 from tests import geometry_ref as G
 from tests import pose_ref as PR
 from tests import pose_refine_ref as RR
+from tests.helpers import check_refine_entry_point_validates_arguments, dev, kernel_resources, to_np
 
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THR = 1.5 / 800                                              # 1.5 px at the scenes' focal length
 ROT_BOUND_DEG, TRANS_BOUND_DEG = 0.1, 1.0                    # the per-scene bounds of tests/test_pose.py
 SCENES = list(range(11, 15)) + list(range(100, 116))
@@ -118,23 +113,12 @@ def test_refinement_improves_the_mean_pose_error_over_20_scenes():
 
 
 def test_refine_pose_entry_point_validates_arguments_without_a_gpu():
-    lib = _lib.load()
-    buf = (ctypes.c_double * 32)()
-    a = ctypes.cast(buf, ctypes.c_void_p)
+    def bind(lib, a):
+        def call(xa=a, R=a, out=a, P=1, N=100, thr=1e-3, iters=15):
+            return lib.roma_refine_pose(xa, a, a, a, R, a, None, P, N, thr, iters, out, a, a, a, a, a, None)
+        return call
 
-    def call(xa=a, R=a, out=a, P=1, N=100, thr=1e-3, iters=15):
-        return lib.roma_refine_pose(xa, a, a, a, R, a, None, P, N, thr, iters, out, a, a, a, a, a, None)
-
-    assert call(xa=None) == _lib.ROMA_E_ARG and b"roma_refine_pose: null pointer" in lib.roma_last_error()
-    assert call(R=None) == _lib.ROMA_E_ARG and b"null pointer" in lib.roma_last_error()
-    assert call(out=None) == _lib.ROMA_E_ARG and b"null pointer" in lib.roma_last_error()
-    assert call(P=0) == _lib.ROMA_E_SHAPE and b"bad shape" in lib.roma_last_error()
-    assert call(N=4) == _lib.ROMA_E_SHAPE and b"need at least 5" in lib.roma_last_error()
-    for thr in (0.0, -1.0, float("nan")):
-        assert call(thr=thr) == _lib.ROMA_E_ARG and b"threshold" in lib.roma_last_error()
-    assert call(iters=-1) == _lib.ROMA_E_ARG and b"iters" in lib.roma_last_error()
-    odd = ctypes.c_void_p(ctypes.addressof(buf) + 8)
-    assert call(xa=odd) == _lib.ROMA_E_ALIGN and b"16-byte" in lib.roma_last_error()
+    check_refine_entry_point_validates_arguments("roma_refine_pose", bind, 5, null=("xa", "R", "out"), misaligned=("xa",))
 
 
 def test_new_functions_refuse_cpu_tensors():
@@ -172,21 +156,7 @@ def test_estimate_relative_pose_rejects_unknown_options_and_cameras():
 
 def test_refine_kernel_uses_no_scratch_and_spills_nothing():
     """The compiler's resource report of csrc/pose_refine.hip (the recipe of test_pose.py)."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    assert os.path.exists(hipcc), f"{hipcc} is missing: the resource report needs the compiler"
-    src = os.path.join(ROOT, "roma_amd", "csrc", "pose_refine.hip")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    kernels = kernel_resources("pose_refine.hip")
     assert any("refine_pose_kernel" in k for k in kernels), sorted(kernels)
     for name, k in kernels.items():
         print(name, k)
@@ -194,16 +164,8 @@ def test_refine_kernel_uses_no_scratch_and_spills_nothing():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 def _K():
-    return _dev(PR.K_SCENE)
-
-
-def _np(*ts):
-    return [t.cpu().numpy() for t in ts]
+    return dev(PR.K_SCENE)
 
 
 def _assert_never_worse(R0, t0, R, t, xa, xb, K=PR.K_SCENE, mask=None, thr=THR):
@@ -225,10 +187,10 @@ def test_refine_parity_with_the_restatement():
     figs, checks = [], []
     for seed in (11, 12, 13, 14):
         xa, xb = G.two_view_scene(seed)[:2]
-        R0, t0, _ = geometry.estimate_pose(_dev(xa), _dev(xb), K, K, THR, seed=seed)
-        R, t, mask, info = geometry.refine_pose(R0, t0, _dev(xa), _dev(xb), K, K, THR, return_info=True)
+        R0, t0, _ = geometry.estimate_pose(dev(xa), dev(xb), K, K, THR, seed=seed)
+        R, t, mask, info = geometry.refine_pose(R0, t0, dev(xa), dev(xb), K, K, THR, return_info=True)
         assert R.shape == (3, 3) and R.dtype == torch.float64 and t.shape == (3,) and mask.shape == (5000,) and mask.dtype == torch.bool
-        R0, t0, R, t, mask = _np(R0, t0, R, t, mask)
+        R0, t0, R, t, mask = to_np(R0, t0, R, t, mask)
         o = RR.refine(R0, t0, xa, xb, K, K, THR)
         _assert_never_worse(R0, t0, R, t, xa, xb)
         _assert_pose(R, t)
@@ -260,13 +222,13 @@ def test_estimate_relative_pose_accuracy_over_20_scenes():
     rows = []
     for seed, (xa, xb) in zip(SCENES, scenes):
         _, R_true, t_true = PR.scene_pose(seed)
-        R0, t0, _ = geometry.estimate_pose(_dev(xa).float(), _dev(xb).float(), K, K, THR, max_iters=2000, seed=seed)
-        pose, info = geometry.estimate_relative_pose(_dev(xa).float(), _dev(xb).float(), CAMERA, CAMERA,
+        R0, t0, _ = geometry.estimate_pose(dev(xa).float(), dev(xb).float(), K, K, THR, max_iters=2000, seed=seed)
+        pose, info = geometry.estimate_relative_pose(dev(xa).float(), dev(xb).float(), CAMERA, CAMERA,
                                                      {"max_epipolar_error": 1.5, "max_iterations": 2000}, seed=seed)
         assert pose.Rt.shape == (3, 4) and torch.equal(pose.Rt[:, :3], pose.R) and torch.equal(pose.Rt[:, 3], pose.t)
         assert all(torch.is_tensor(info[k]) and info[k].is_cuda for k in ("inliers", "num_inliers", "model_score", "refinements"))
         assert info["iterations"] == 2000 and int(info["num_inliers"]) == int(info["inliers"].sum())
-        R0, t0, R, t = _np(R0, t0, pose.R, pose.t)
+        R0, t0, R, t = to_np(R0, t0, pose.R, pose.t)
         xa32, xb32 = xa.astype(np.float32).astype(np.float64), xb.astype(np.float32).astype(np.float64)
         _assert_never_worse(R0, t0, R, t, xa32, xb32)
         _assert_pose(R, t)
@@ -291,35 +253,35 @@ def test_refine_determinism_and_batch_independence():
     from roma_amd import geometry
     xa, xb = _batch(20)
     K = _K()
-    R0, t0, _ = geometry.estimate_pose(_dev(xa), _dev(xb), K, K, THR, max_iters=500, seed=5)
-    o1 = geometry.refine_pose(R0, t0, _dev(xa), _dev(xb), K, K, THR, return_info=True)
-    o2 = geometry.refine_pose(R0, t0, _dev(xa), _dev(xb), K, K, THR, return_info=True)
+    R0, t0, _ = geometry.estimate_pose(dev(xa), dev(xb), K, K, THR, max_iters=500, seed=5)
+    o1 = geometry.refine_pose(R0, t0, dev(xa), dev(xb), K, K, THR, return_info=True)
+    o2 = geometry.refine_pose(R0, t0, dev(xa), dev(xb), K, K, THR, return_info=True)
     assert o1[0].shape == (8, 3, 3) and o1[1].shape == (8, 3) and o1[2].shape == (8, 2000) and o1[3]["steps"].shape == (8,)
     assert all(torch.equal(a, b) for a, b in zip(o1[:3], o2[:3])) and all(torch.equal(o1[3][k], o2[3][k]) for k in o1[3])
     assert int(o1[3]["steps"].min()) >= 1
     for i in range(8):
-        _assert_never_worse(*_np(R0[i], t0[i], o1[0][i], o1[1][i]), xa[i], xb[i])
-        _assert_pose(*_np(o1[0][i], o1[1][i]))
+        _assert_never_worse(*to_np(R0[i], t0[i], o1[0][i], o1[1][i]), xa[i], xb[i])
+        _assert_pose(*to_np(o1[0][i], o1[1][i]))
     # pair 3 alone, and inside another batch with other intrinsics next to it
-    s = geometry.refine_pose(R0[3], t0[3], _dev(xa[3]), _dev(xb[3]), K, K, THR, return_info=True)
+    s = geometry.refine_pose(R0[3], t0[3], dev(xa[3]), dev(xb[3]), K, K, THR, return_info=True)
     assert all(torch.equal(a, b[3]) for a, b in zip(s[:3], o1[:3])) and all(torch.equal(s[3][k], o1[3][k][3]) for k in s[3])
     xa2, xb2 = _batch(40)
     xa2[3], xb2[3] = xa[3], xb[3]
     Ks = K.expand(8, 3, 3).clone()
     Ks[5, 0, 0] = 700.0
-    o3 = geometry.refine_pose(R0, t0, _dev(xa2), _dev(xb2), Ks, Ks, THR, return_info=True)
+    o3 = geometry.refine_pose(R0, t0, dev(xa2), dev(xb2), Ks, Ks, THR, return_info=True)
     assert all(torch.equal(a[3], b[3]) for a, b in zip(o1[:3], o3[:3])) and all(torch.equal(o1[3][k][3], o3[3][k][3]) for k in o1[3])
     for i in range(8):                                     # a pose of another scene: whatever happens, never worse
-        _assert_never_worse(*_np(R0[i], t0[i], o3[0][i], o3[1][i]), xa2[i], xb2[i], K=Ks[i].cpu().numpy())
+        _assert_never_worse(*to_np(R0[i], t0[i], o3[0][i], o3[1][i]), xa2[i], xb2[i], K=Ks[i].cpu().numpy())
     # the mask restricts the matches that carry weight
     only = torch.zeros(8, 2000, dtype=torch.bool, device=DEV)
     only[:, :1000] = True
-    Rm, tm, mm = geometry.refine_pose(R0, t0, _dev(xa), _dev(xb), K, K, THR, mask=only)
+    Rm, tm, mm = geometry.refine_pose(R0, t0, dev(xa), dev(xb), K, K, THR, mask=only)
     assert not bool(mm[:, 1000:].any()) and int(mm.sum()) > 0
-    Rh, th, mh = geometry.refine_pose(R0, t0, _dev(xa[:, :1000]), _dev(xb[:, :1000]), K, K, THR)
+    Rh, th, mh = geometry.refine_pose(R0, t0, dev(xa[:, :1000]), dev(xb[:, :1000]), K, K, THR)
     assert torch.equal(Rm, Rh) and torch.equal(tm, th) and torch.equal(mm[:, :1000], mh)
     for i in range(8):
-        _assert_never_worse(*_np(R0[i], t0[i], Rm[i], tm[i]), xa[i], xb[i], mask=only[i].cpu().numpy())
+        _assert_never_worse(*to_np(R0[i], t0[i], Rm[i], tm[i]), xa[i], xb[i], mask=only[i].cpu().numpy())
 
 
 @pytest.mark.gpu
@@ -328,17 +290,17 @@ def test_refining_a_refined_pose_stays_at_the_optimum():
     K = PR.K_SCENE
     for seed in (11, 12):
         xa, xb = G.two_view_scene(seed)[:2]
-        R0, t0, _ = geometry.estimate_pose(_dev(xa), _dev(xb), K, K, THR, seed=seed)
-        R1, t1, _ = geometry.refine_pose(R0, t0, _dev(xa), _dev(xb), K, K, THR, iters=30)
-        R2, t2, m2, info = geometry.refine_pose(R1, t1, _dev(xa), _dev(xb), K, K, THR, return_info=True)
-        R1, t1, R2, t2 = _np(R1, t1, R2, t2)
+        R0, t0, _ = geometry.estimate_pose(dev(xa), dev(xb), K, K, THR, seed=seed)
+        R1, t1, _ = geometry.refine_pose(R0, t0, dev(xa), dev(xb), K, K, THR, iters=30)
+        R2, t2, m2, info = geometry.refine_pose(R1, t1, dev(xa), dev(xb), K, K, THR, return_info=True)
+        R1, t1, R2, t2 = to_np(R1, t1, R2, t2)
         _assert_never_worse(R1, t1, R2, t2, xa, xb)
         _assert_pose(R2, t2)
         print(f"scene {seed}: a second refinement moves the pose by {_rot_deg(R2, R1):.3e} deg / {_angle_deg(t2, t1):.3e} deg "
               f"in {int(info['steps'])} steps")
         assert _rot_deg(R2, R1) <= PARITY_ROT_DEG and _angle_deg(t2, t1) <= PARITY_TRANS_DEG
         # iters = 0 is the identity, with the pose's own mask and cost
-        R3, t3, m3, i3 = geometry.refine_pose(_dev(R1), _dev(t1), _dev(xa), _dev(xb), K, K, THR, iters=0, return_info=True)
+        R3, t3, m3, i3 = geometry.refine_pose(dev(R1), dev(t1), dev(xa), dev(xb), K, K, THR, iters=0, return_info=True)
         assert np.array_equal(R3.cpu().numpy(), R1) and np.array_equal(t3.cpu().numpy(), t1) and int(i3["steps"]) == 0
         assert int(i3["count"]) == int(m3.sum())
 
@@ -350,33 +312,33 @@ def test_refine_of_degenerate_input_returns_the_input():
     K = _K()
     xa, xb = G.two_view_scene(3, N=500)[:2]
     _, R_true, t_true = PR.scene_pose(3)
-    R0, t0 = _dev(R_true), _dev(t_true / np.linalg.norm(t_true))
+    R0, t0 = dev(R_true), dev(t_true / np.linalg.norm(t_true))
     nan = torch.full((500, 2), float("nan"), device=DEV, dtype=torch.float64)
     R, t, mask, info = geometry.refine_pose(R0, t0, nan, nan, K, K, THR, return_info=True)          # no finite match
     assert torch.equal(R, R0) and torch.equal(t, t0) and not bool(mask.any()) and int(info["steps"]) == 0 and float(info["cost"]) == 0.0
     few = torch.zeros(500, dtype=torch.bool, device=DEV)
     few[:4] = True
-    R, t, mask, info = geometry.refine_pose(R0, t0, _dev(xa), _dev(xb), K, K, THR, mask=few, return_info=True)   # < 5 weighted matches
+    R, t, mask, info = geometry.refine_pose(R0, t0, dev(xa), dev(xb), K, K, THR, mask=few, return_info=True)   # < 5 weighted matches
     assert torch.equal(R, R0) and torch.equal(t, t0) and int(mask.sum()) <= 4 and int(info["steps"]) == 0
     singular = K.clone()
     singular[1, 1] = 0.0
-    Rz, tz, mz = geometry.estimate_pose(_dev(xa), _dev(xb), singular, K, THR, max_iters=100, seed=0)  # zero E: R = I, t = 0
+    Rz, tz, mz = geometry.estimate_pose(dev(xa), dev(xb), singular, K, THR, max_iters=100, seed=0)  # zero E: R = I, t = 0
     assert torch.equal(tz, torch.zeros_like(tz))
-    R, t, mask, info = geometry.refine_pose(Rz, tz, _dev(xa), _dev(xb), singular, K, THR, return_info=True)
+    R, t, mask, info = geometry.refine_pose(Rz, tz, dev(xa), dev(xb), singular, K, THR, return_info=True)
     assert torch.equal(R, Rz) and torch.equal(t, tz) and not bool(mask.any()) and int(info["steps"]) == 0
-    R, t, mask = geometry.refine_pose(Rz, tz, _dev(xa), _dev(xb), K, K, THR)                        # t = 0 with a good K
+    R, t, mask = geometry.refine_pose(Rz, tz, dev(xa), dev(xb), K, K, THR)                        # t = 0 with a good K
     assert torch.equal(R, Rz) and torch.equal(t, tz)
     Rn = R0.clone()
     Rn[1, 1] = float("nan")
-    R, t, mask = geometry.refine_pose(Rn, t0, _dev(xa), _dev(xb), K, K, THR)                        # a pose that is not finite
+    R, t, mask = geometry.refine_pose(Rn, t0, dev(xa), dev(xb), K, K, THR)                        # a pose that is not finite
     assert torch.equal(R.isnan(), Rn.isnan()) and torch.equal(t, t0) and not bool(mask.any())
     pose, info = geometry.estimate_relative_pose(nan, nan, CAMERA, CAMERA, {"max_iterations": 100}, seed=0)
     assert torch.equal(pose.R, torch.eye(3, dtype=torch.float64, device=DEV)) and torch.equal(pose.t, torch.zeros_like(pose.t))
     assert int(info["num_inliers"]) == 0 and int(info["refinements"]) == 0
     # min_inliers above what the pair has: the RANSAC pose comes back unrefined
-    Re, te, _ = geometry.estimate_pose(_dev(xa), _dev(xb), K, K, THR, max_iters=200, seed=1)
+    Re, te, _ = geometry.estimate_pose(dev(xa), dev(xb), K, K, THR, max_iters=200, seed=1)
     cam = dict(CAMERA)
-    pose, info = geometry.estimate_relative_pose(_dev(xa), _dev(xb), cam, cam, {"max_epipolar_error": 1.5, "max_iterations": 200,
+    pose, info = geometry.estimate_relative_pose(dev(xa), dev(xb), cam, cam, {"max_epipolar_error": 1.5, "max_iterations": 200,
                                                                                  "min_inliers": 501}, seed=1)
     assert torch.equal(pose.R, Re) and torch.equal(pose.t, te) and int(info["refinements"]) == 0
 
@@ -385,7 +347,7 @@ def test_refine_of_degenerate_input_returns_the_input():
 def test_refine_graph_capture_replays_the_eager_result():
     from roma_amd import geometry
     xa, xb = G.two_view_scene(30, N=3000)[:2]
-    xa, xb, K = _dev(xa), _dev(xb), _K()
+    xa, xb, K = dev(xa), dev(xb), _K()
     R0, t0, _ = geometry.estimate_pose(xa, xb, K, K, THR, max_iters=500, seed=11)
     eager = geometry.refine_pose(R0, t0, xa, xb, K, K, THR)
     s = torch.cuda.Stream()
@@ -399,7 +361,7 @@ def test_refine_graph_capture_replays_the_eager_result():
     g.replay()
     torch.cuda.synchronize()
     assert all(torch.equal(a, b) for a, b in zip(out, eager))
-    _assert_never_worse(*_np(R0, t0, out[0], out[1]), xa.cpu().numpy(), xb.cpu().numpy())
+    _assert_never_worse(*to_np(R0, t0, out[0], out[1]), xa.cpu().numpy(), xb.cpu().numpy())
     assert PR.rotation_error_deg(out[0].cpu().numpy(), PR.scene_pose(30)[1]) < 0.5
 
 
@@ -416,10 +378,10 @@ def test_pose_error_matches_the_numpy_errors():
         ts.append(t)
         Tg.append(np.concatenate([R_true, t_true[:, None]], -1))
         want.append((PR.translation_error_deg(t, t_true), PR.rotation_error_deg(R, R_true)))
-    e_t, e_R = geometry.pose_error(_dev(np.stack(Rs)), _dev(np.stack(ts)), np.stack(Tg))
+    e_t, e_R = geometry.pose_error(dev(np.stack(Rs)), dev(np.stack(ts)), np.stack(Tg))
     assert e_t.shape == (6,) and e_t.is_cuda
     assert np.abs(e_t.cpu().numpy() - [w[0] for w in want]).max() < 1e-6 and np.abs(e_R.cpu().numpy() - [w[1] for w in want]).max() < 1e-6
-    e_t1, e_R1 = geometry.pose_error(_dev(Rs[0]), _dev(ts[0]), _dev(np.vstack([Tg[0], [0, 0, 0, 1]])))
+    e_t1, e_R1 = geometry.pose_error(dev(Rs[0]), dev(ts[0]), dev(np.vstack([Tg[0], [0, 0, 0, 1]])))
     assert abs(float(e_t1) - want[0][0]) < 1e-6 and abs(float(e_R1) - want[0][1]) < 1e-6 and want[0][0] < 90
 
 
@@ -451,7 +413,7 @@ def test_relative_pose_integration_with_match_and_sample():
     K = np.array([[500.0, 0, 320], [0, 500.0, 240], [0, 0, 1]])
     R0, t0, _ = geometry.estimate_pose(torch.stack(kA), torch.stack(kB), K, K, 1.0 / 500, max_iters=500, seed=0)
     for i in range(2):
-        _assert_never_worse(*_np(R0[i], t0[i], pose.R[i], pose.t[i]), kA[i].double().cpu().numpy(), kB[i].double().cpu().numpy(), K=K,
+        _assert_never_worse(*to_np(R0[i], t0[i], pose.R[i], pose.t[i]), kA[i].double().cpu().numpy(), kB[i].double().cpu().numpy(), K=K,
                             thr=1.0 / 500)
     p1, i1 = geometry.estimate_relative_pose(kA[0], kB[0], cam, cam, opt, seed=0)
     assert torch.equal(p1.R, pose.R[0]) and torch.equal(p1.t, pose.t[0]) and torch.equal(i1["inliers"], info["inliers"][0])

@@ -15,9 +15,6 @@ the CPU: about 6e-5 for points and depths, 1e-4 px for reproj_error, 2e-7 for co
 import ctypes
 import functools
 import math
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -27,9 +24,9 @@ from roma_amd import _lib
 from tests import geometry_ref as G
 from tests import pose_ref as PR
 from tests import triangulate_ref as T
+from tests.helpers import dev, kernel_resources
 
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("points", "depth_a", "depth_b", "reproj", "cos_parallax")
 MIN_PARALLAX_DEG = 2.0
 COS_MIN_PARALLAX = math.cos(math.radians(MIN_PARALLAX_DEG))
@@ -171,21 +168,7 @@ def test_new_functions_refuse_cpu_tensors_and_bad_arguments():
 
 def test_triangulate_kernel_uses_no_scratch_and_spills_nothing():
     """The compiler's resource report of csrc/triangulate.hip (the recipe of test_pose.py); LDS holds the pair constants only."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    assert os.path.exists(hipcc), f"{hipcc} is missing: the resource report needs the compiler"
-    src = os.path.join(ROOT, "roma_amd", "csrc", "triangulate.hip")
-    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        mm = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if mm:
-            cur = kernels.setdefault(mm.group(1), {})
-            continue
-        mm = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?:\s+(\d+)", line)
-        if mm and cur is not None:
-            cur[mm.group(1).strip()] = int(mm.group(2))
+    kernels = kernel_resources("triangulate.hip")
     assert sum("triangulate_kernel" in k for k in kernels) == 2, sorted(kernels)
     for name, k in kernels.items():
         print(name, k)
@@ -193,10 +176,6 @@ def test_triangulate_kernel_uses_no_scratch_and_spills_nothing():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
 def _fields(tri):
     """a Triangulation -> the restatement's dict of numpy arrays"""
     return {"points": tri.points.cpu().numpy(), "depth_a": tri.depth_A.cpu().numpy(), "depth_b": tri.depth_B.cpu().numpy(),
@@ -205,8 +184,8 @@ def _fields(tri):
 
 def _run(m, K, R, t, **kw):
     from roma_amd import geometry
-    m = _dev(m)
-    return geometry.triangulate(m[..., :2], m[..., 2:], _dev(R), _dev(t), _dev(K), _dev(K), **kw)
+    m = dev(m)
+    return geometry.triangulate(m[..., :2], m[..., 2:], dev(R), dev(t), dev(K), dev(K), **kw)
 
 
 def _assert_within(o, r, sel, tol, what):
@@ -297,7 +276,7 @@ def _three_pairs(N):
 def test_triangulate_shapes_batches_null_outputs_and_guard_bands(N):
     full_m, Ka, Kb, R, t = _three_pairs(1000)
     m = full_m[:, :N]
-    dm, dKa, dKb, dR, dt = (_dev(v) for v in (m, Ka, Kb, R, t))
+    dm, dKa, dKb, dR, dt = (dev(v) for v in (m, Ka, Kb, R, t))
     for method in (0, 1):
         every = _raw(dm, dKa, dKb, dR, dt, method, max_reproj=3.0, max_cos=COS_MIN_PARALLAX)
         assert all(torch.isfinite(every[k]).all() for k in FIELDS) and int(every["valid"].max()) <= 1
@@ -314,7 +293,7 @@ def test_triangulate_shapes_batches_null_outputs_and_guard_bands(N):
             assert list(one) == [k] and torch.equal(one[k], every[k]), (method, k)
         # the first N matches of the N = 1000 call
         if N < 1000:
-            big = _raw(_dev(full_m), dKa, dKb, dR, dt, method, max_reproj=3.0, max_cos=COS_MIN_PARALLAX)
+            big = _raw(dev(full_m), dKa, dKb, dR, dt, method, max_reproj=3.0, max_cos=COS_MIN_PARALLAX)
             assert all(torch.equal(big[k][:, :N], every[k]) for k in every), method
         # and the pairs really differ: against the restatement with each pair's own cameras and pose
         if N == 1000:
@@ -343,7 +322,7 @@ def test_triangulate_defined_behaviour_on_bad_input():
             assert np.array_equal(o[k][keep], base[k][keep]), (method, k)         # and nobody else notices
         # mask 0 -> valid 0, values as without the mask
         mask = np.arange(1000) % 3 != 0
-        o = _fields(_run(m, K, R, t, method=method, mask=_dev(mask)))
+        o = _fields(_run(m, K, R, t, method=method, mask=dev(mask)))
         assert np.array_equal(o["valid"], base["valid"] & mask) and all(np.array_equal(o[k], base[k]) for k in FIELDS)
         # t = 0: no NaN or inf anywhere and no valid match
         o = _fields(_run(m, K, R, np.zeros(3), method=method))
@@ -352,8 +331,8 @@ def test_triangulate_defined_behaviour_on_bad_input():
         Ks = K.copy()
         Ks[1, 1] = 0.0
         from roma_amd import geometry
-        dm = _dev(m)
-        tri = geometry.triangulate(dm[:, :2], dm[:, 2:], _dev(R), _dev(t), _dev(Ks), _dev(K), method=method)
+        dm = dev(m)
+        tri = geometry.triangulate(dm[:, :2], dm[:, 2:], dev(R), dev(t), dev(Ks), dev(K), method=method)
         assert all(not _fields(tri)[k].any() for k in FIELDS + ("valid",))
         # the gates narrow valid monotonically, exactly by the reported quantities, and change nothing else
         last = base["valid"]
@@ -450,7 +429,7 @@ def test_depth_from_warp_on_a_synthetic_warp():
         zA, zB = r64["depth_a"].reshape(H, 2 * W)[:, :W], r64["depth_b"].reshape(H, 2 * W)[:, W:]
         assert np.abs(zA / dA - 1).max() < 1e-5 and np.abs(zB / dB - 1).max() < 1e-5
         cert = torch.ones(H, 2 * W, device=DEV)
-        out = geometry.depth_from_warp(_dev(warp), cert, _dev(R), _dev(t), _dev(K), _dev(K), H_IMG, W_IMG)
+        out = geometry.depth_from_warp(dev(warp), cert, dev(R), dev(t), dev(K), dev(K), H_IMG, W_IMG)
         assert out.depth_A.shape == (H, W) and out.depth_B.shape == (H, W) and out.valid_A.shape == (H, W) and out.valid_B.shape == (H, W)
         assert out.points.shape == (H, 2 * W, 3) and out.valid.shape == (H, 2 * W) and out.depth_A.dtype == torch.float32
         assert bool(out.valid.all()) and torch.equal(out.valid[:, :W], out.valid_A) and torch.equal(out.valid[:, W:], out.valid_B)
@@ -462,8 +441,8 @@ def test_depth_from_warp_on_a_synthetic_warp():
         assert float(np.abs(out.depth_A.cpu().numpy() / dA - 1).max()) <= tol["depth_a"] + 1e-5
         assert float(np.abs(out.depth_B.cpu().numpy() / dB - 1).max()) <= tol["depth_b"] + 1e-5
         # triangulate on to_pixel_coordinates of the flattened warp: the same up to the fused s * c + o of the kernel
-        kA, kB = RegressionMatcher(None, None).to_pixel_coordinates(_dev(warp).reshape(-1, 4), H_IMG, W_IMG, H_IMG, W_IMG)
-        tri = geometry.triangulate(kA, kB, _dev(R), _dev(t), _dev(K), _dev(K))
+        kA, kB = RegressionMatcher(None, None).to_pixel_coordinates(dev(warp).reshape(-1, 4), H_IMG, W_IMG, H_IMG, W_IMG)
+        tri = geometry.triangulate(kA, kB, dev(R), dev(t), dev(K), dev(K))
         o = _fields(tri)
         flat = {"points": out.points.cpu().numpy().reshape(-1, 3)}
         assert float((np.linalg.norm(flat["points"] - o["points"], axis=-1) / np.linalg.norm(o["points"], axis=-1)).max()) <= tol["points"]
@@ -472,22 +451,22 @@ def test_depth_from_warp_on_a_synthetic_warp():
         # a certainty below the threshold, or a cleared mask, zeroes exactly those pixels
         rng = np.random.default_rng(seed)
         low, off = rng.random((H, 2 * W)) < 0.2, rng.random((H, 2 * W)) < 0.2
-        cert2 = torch.where(_dev(low), 0.04, 0.06)
-        for kw, gone in (({}, low), ({"mask": _dev(~off)}, low | off), ({"mask": _dev((~off).astype(np.float32))}, low | off)):
-            part = geometry.depth_from_warp(_dev(warp), cert2, _dev(R), _dev(t), _dev(K), _dev(K), H_IMG, W_IMG, H_IMG, W_IMG, **kw)
-            gone_d = _dev(gone)
+        cert2 = torch.where(dev(low), 0.04, 0.06)
+        for kw, gone in (({}, low), ({"mask": dev(~off)}, low | off), ({"mask": dev((~off).astype(np.float32))}, low | off)):
+            part = geometry.depth_from_warp(dev(warp), cert2, dev(R), dev(t), dev(K), dev(K), H_IMG, W_IMG, H_IMG, W_IMG, **kw)
+            gone_d = dev(gone)
             assert torch.equal(part.valid, ~gone_d) and torch.equal(part.points, out.points)
             assert torch.equal(part.depth_A, torch.where(gone_d[:, :W], 0.0, out.depth_A))
             assert torch.equal(part.depth_B, torch.where(gone_d[:, W:], 0.0, out.depth_B))
-        none = geometry.depth_from_warp(_dev(warp), cert2, _dev(R), _dev(t), _dev(K), _dev(K), H_IMG, W_IMG, certainty_thresh=0.5)
+        none = geometry.depth_from_warp(dev(warp), cert2, dev(R), dev(t), dev(K), dev(K), H_IMG, W_IMG, certainty_thresh=0.5)
         assert not bool(none.valid.any()) and not bool(none.depth_A.any()) and not bool(none.depth_B.any())
         # a warp that is not symmetric: the A half only
-        half = geometry.depth_from_warp(_dev(warp[:, :W]), cert[:, :W], _dev(R), _dev(t), _dev(K), _dev(K), H_IMG, W_IMG, symmetric=False)
+        half = geometry.depth_from_warp(dev(warp[:, :W]), cert[:, :W], dev(R), dev(t), dev(K), dev(K), H_IMG, W_IMG, symmetric=False)
         assert half.depth_B is None and half.valid_B is None and torch.equal(half.depth_A, out.depth_A) and half.points.shape == (H, W, 3)
         outs.append((warp, K, R, t, out))
     # the stack of both, each with its own pose
-    stack = geometry.depth_from_warp(_dev(np.stack([o[0] for o in outs])), torch.ones(2, H, 2 * W, device=DEV), _dev(np.stack([o[2] for o in outs])),
-                                     _dev(np.stack([o[3] for o in outs])), _dev(outs[0][1]), _dev(outs[0][1]), H_IMG, W_IMG)
+    stack = geometry.depth_from_warp(dev(np.stack([o[0] for o in outs])), torch.ones(2, H, 2 * W, device=DEV), dev(np.stack([o[2] for o in outs])),
+                                     dev(np.stack([o[3] for o in outs])), dev(outs[0][1]), dev(outs[0][1]), H_IMG, W_IMG)
     assert stack.depth_A.shape == (2, H, W) and stack.points.shape == (2, H, 2 * W, 3) and stack.valid.shape == (2, H, 2 * W)
     for i, (_, _, _, _, out) in enumerate(outs):
         assert torch.equal(stack.depth_A[i], out.depth_A) and torch.equal(stack.depth_B[i], out.depth_B)
@@ -528,10 +507,10 @@ def test_depth_from_warp_on_a_real_match():
 def test_triangulation_graph_capture_replays_the_eager_result():
     from roma_amd import geometry
     m, _, _, K, R, t = scene(2)
-    dm, dK, dR, dt = _dev(m), _dev(K), _dev(R), _dev(t)
+    dm, dK, dR, dt = dev(m), dev(K), dev(R), dev(t)
     xa, xb = dm[:, :2].contiguous(), dm[:, 2:].contiguous()
     warp, _, _, Kw, Rw, tw = synthetic_warp(0)
-    dw, cert, dKw, dRw, dtw = _dev(warp), torch.full((16, 32), 0.5, device=DEV), _dev(Kw), _dev(Rw), _dev(tw)
+    dw, cert, dKw, dRw, dtw = dev(warp), torch.full((16, 32), 0.5, device=DEV), dev(Kw), dev(Rw), dev(tw)
 
     def both():
         a = geometry.triangulate(xa, xb, dR, dt, dK, dK, max_reproj_error=2.0, min_parallax_deg=1.0)
