@@ -277,6 +277,16 @@ int roma_refiner_block_wide(const void* x, const void* w25p, const float* scale,
 int roma_pointwise_mfma(const void* x, const void* wt, const float* bias, void* y, long M, int C, int kpad, int dtype,
                         int x_pitch, int y_pitch, void* stream);
 
+/* The whole ConvRefiner block at mid widths in ONE launch — matcher.py:77-103, 139-140 — for 32 < C <= 160 (C a multiple of 8),
+ * fp16 / bf16: roma_dwconv5x5_bn_relu and roma_pointwise_mfma (kpad 160) joined through on-chip memory, with their operands and
+ * their bits:  y = bias + relu(dwconv5x5(x, w25) * scale + shift) @ wt^T, the intermediate rounded to `dtype`.
+ *   x, y: (B,H,W,pitch) channels-last `dtype`, pitches multiples of 8 and >= C, bases 16-byte aligned, each below 4 GB; the two
+ *   must not overlap.  Channels [C, y_pitch) of y are not written.
+ *   w25: (25, C) fp32 tap-major; scale, shift: (C) fp32; wt: (160, 160) `dtype`, wt[n][k] zero-padded; bias: (160) fp32. */
+int roma_refiner_block_mid(const void* x, const float* w25, const float* scale, const float* shift, const void* wt,
+                           const float* bias, void* y, int B, int C, int H, int W, int dtype, int x_pitch, int y_pitch,
+                           void* stream);
+
 /* ConvRefiner head + Decoder update fused — matcher.py:141 (out_conv, D -> 3, fp32 on d.float()) and :397-402:
  *   d = bo + x[m,:] @ wo;  flow[b,0] += sx*d0;  flow[b,1] += sy*d1;  cert_out = (cert_in ? cert_in : 0) + d2
  *   x: (B*H*W, pitch) channels-last rows of `dtype` (C channels used), wo (C,3) fp32 row-major, bo (3) fp32,

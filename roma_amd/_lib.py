@@ -59,6 +59,8 @@ SIGNATURES = {
     "roma_pointwise_mfma": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_int, c_void_p],
     "roma_refiner_block": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                            c_int, c_int, c_void_p],
+    "roma_refiner_block_mid": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_int, c_void_p],
     "roma_refiner_wide_pack": [c_void_p, c_void_p, c_int],
     "roma_refiner_wide_taps": [c_void_p, c_void_p, c_int],
     "roma_jpeg_info": [c_void_p, c_long, c_void_p],

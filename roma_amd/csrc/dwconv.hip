@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "refiner_mid_device.h"
 
 namespace roma {
 namespace {
@@ -141,8 +142,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void dwconv5x5_lds_kernel(co
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            T* __restrict__ y, int B, int C, int H, int W, int x_pitch, int y_pitch,
                                                            unsigned total, unsigned band) {
-  constexpr int E = 8, XS = 8, NC = XS + 4;
-  static_assert(sizeof(T) == 2, "16-bit activations");
+  constexpr int E = 8, XS = mid::kStrip;
   extern __shared__ __attribute__((aligned(16))) float s_w[];     // [25][C]
   const int tid = threadIdx.x;
   {                                                               // taps -> LDS, 8 loads in flight per thread (one load per round
@@ -173,91 +173,11 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 1) void dwconv5x5_lds_kernel(co
     r /= WS;
     const int ys = (int)(r % (unsigned)H), b = (int)(r / (unsigned)H);
     const int c0 = (int)k * E;
-    float acc[XS][E];
-#pragma unroll
-    for (int o = 0; o < XS; ++o)
-#pragma unroll
-      for (int e = 0; e < E; ++e) acc[o][e] = 0.f;
-    const bool interior = ys >= 2 && ys + 3 <= H && xs >= 2 && xs + XS + 2 <= W;
-    // 5 taps x 8 channels of fused multiply-adds for every column of one input row (taps of tap-row iy from LDS)
-    auto fma_row = [&](const u32x4 (&src)[NC], int iy, auto masked_c) {
-      const int yi = ys + iy - 2;
-      const float my = (yi >= 0 && yi < H) ? 1.f : 0.f;
-      const float* wr = s_w + (size_t)iy * 5 * C + c0;
-      float wv[5][E];
-#pragma unroll
-      for (int dx = 0; dx < 5; ++dx)
-#pragma unroll
-        for (int e = 0; e < E; e += 4) *reinterpret_cast<float4_t*>(&wv[dx][e]) = *reinterpret_cast<const float4_t*>(wr + dx * C + e);
-#pragma unroll
-      for (int cx = 0; cx < NC; ++cx) {
-        float f[E];
-        unpack16<T>(src[cx], f);
-        if constexpr (decltype(masked_c)::value) {
-          const int xi = xs - 2 + cx;
-          const float m = (xi >= 0 && xi < W) ? my : 0.f;
-#pragma unroll
-          for (int e = 0; e < E; ++e) f[e] *= m;
-        }
-#pragma unroll
-        for (int dx = 0; dx < 5; ++dx) {
-          const int o = cx - dx;
-          if (o >= 0 && o < XS) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) acc[o][e] = __builtin_fmaf(wv[dx][e], f[e], acc[o][e]);
-          }
-        }
-      }
-    };
-    if (__all(interior)) {                                         // wave-uniform: a wave with one border strip takes the border path whole
-      // all but a 2-pixel frame.  Byte offset of (b, row, column xs - 2, packet k) from x in 32 bits (the host checks the tensor is
-      // < 4 GB); the 12 columns of a row are the uniform distances cx * x_pitch * 2 from it: a load is scalar base + one vector
-      // offset.  Software pipeline: row iy + 1 is requested before row iy is multiplied.  (hipcc converts the whole row to fp32
-      // first — 96 registers — and then issues the 12 loads back to back; pinning a finer interleave needs more registers, not fewer.)
-      unsigned voff = (unsigned)((((size_t)b * H + ys - 2) * W + xs - 2) * x_pitch + c0) * 2u;
-      const unsigned vstep = (unsigned)W * x_pitch * 2u;
-      auto load_row = [&](u32x4 (&dst)[NC]) {
-#pragma unroll
-        for (int cx = 0; cx < NC; ++cx)
-          dst[cx] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(x) + (size_t)cx * x_pitch * 2 + voff);
-        voff += vstep;
-      };
-      u32x4 cur[NC], nxt[NC];
-      load_row(nxt);
-#pragma unroll 1
-      for (int iy = 0; iy < 4; ++iy) {
-#pragma unroll
-        for (int cx = 0; cx < NC; ++cx) cur[cx] = nxt[cx];
-        load_row(nxt);
-        fma_row(cur, iy, std::false_type{});
-      }
-      fma_row(nxt, 4, std::false_type{});
-    } else {
-      // border strips: clamped addresses, taps zeroed through a mask, one row at a time
-#pragma unroll 1
-      for (int iy = 0; iy < 5; ++iy) {
-        const T* row = x + ((size_t)b * H + min(max(ys + iy - 2, 0), H - 1)) * W * x_pitch + c0;
-        u32x4 cur[NC];
-#pragma unroll
-        for (int cx = 0; cx < NC; ++cx) cur[cx] = *reinterpret_cast<const u32x4*>(row + (size_t)min(max(xs - 2 + cx, 0), W - 1) * x_pitch);
-        fma_row(cur, iy, std::true_type{});
-      }
-    }
-    float sc[E], sh[E];
-#pragma unroll
-    for (int e = 0; e < E; e += 4) {
-      *reinterpret_cast<float4_t*>(&sc[e]) = *reinterpret_cast<const float4_t*>(scale + c0 + e);
-      *reinterpret_cast<float4_t*>(&sh[e]) = *reinterpret_cast<const float4_t*>(shift + c0 + e);
-    }
-    T* yrow = y + (((size_t)b * H + ys) * W) * y_pitch + c0;
-#pragma unroll
-    for (int o = 0; o < XS; ++o) {
-      if (xs + o >= W) break;
-      float v[E];
-#pragma unroll
-      for (int e = 0; e < E; ++e) v[e] = fmaxf(__builtin_fmaf(acc[o][e], sc[e], sh[e]), 0.f);
-      store16_stream(yrow + (size_t)(xs + o) * y_pitch, pack16<T>(v));
-    }
+    // the strip body (row load pipeline, 5 x 5 taps in fp32, BN + ReLU + pack) is mid::dw_strip, shared with refiner_mid.hip
+    mid::dw_strip<T>(x, s_w, scale, shift, b, ys, xs, c0, C, H, W, x_pitch, W - xs, [&](int o, const u32x4& v) {
+      T* yrow = y + (((size_t)b * H + ys) * W) * y_pitch + c0;
+      store16_stream(yrow + (size_t)(xs + o) * y_pitch, v);
+    });
   }
 }
 

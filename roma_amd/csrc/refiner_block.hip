@@ -15,6 +15,7 @@
 #include <algorithm>
 #include "common.h"
 #include "lc_device.h"
+#include "refiner_mid_device.h"
 
 namespace roma {
 namespace {
@@ -483,7 +484,7 @@ struct PWParams {
 
 template <typename T, int KP>
 __global__ __launch_bounds__(256, 2) void pointwise_mfma_kernel(PWParams p) {
-  constexpr int KPAD = 32 * KP, NT = KPAD / 16, RS = KPAD / 8 + 1, OS = KPAD + 8;
+  constexpr int KPAD = 32 * KP, RS = KPAD / 8 + 1, OS = KPAD + 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32x4* s_pw = reinterpret_cast<u32x4*>(smem);                         // [KPAD][RS]
   float* s_b = reinterpret_cast<float*>(s_pw + KPAD * RS);              // [KPAD]
@@ -504,27 +505,16 @@ __global__ __launch_bounds__(256, 2) void pointwise_mfma_kernel(PWParams p) {
   for (long tile = (long)blockIdx.x * 4 + wv; tile < ntile; tile += (long)gridDim.x * 4) {
     const long row0 = tile * 16;
     const long r = row0 + m < p.M ? row0 + m : p.M - 1;
-    u32x4 a[KP];
+    u32x4 a[1][KP];
 #pragma unroll
     for (int ks = 0; ks < KP; ++ks) {
       const int pk = 4 * ks + kq;
       u32x4 v = *reinterpret_cast<const u32x4*>(x + r * p.x_pitch + (pk < PKT ? pk : 0) * 8);
       if (pk >= PKT) v = u32x4{0, 0, 0, 0};
-      a[ks] = v;
+      a[0][ks] = v;
     }
-    float4_t acc[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      acc[nt] = float4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KP; ++ks) acc[nt] = mfma_blk(a[ks], s_pw[(nt * 16 + m) * RS + 4 * ks + kq], acc[nt], T{});
-    }
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const float bv = s_b[nt * 16 + m];
-#pragma unroll
-      for (int r4 = 0; r4 < 4; ++r4) so[(4 * kq + r4) * OS + nt * 16 + m] = from_f32<T>(acc[nt][r4] + bv);
-    }
+    T* const stage[1] = {so};
+    mid::pw_row_groups<T, KP, 1>(a, s_pw, s_b, stage, m, kq);             // the MFMA step, shared with refiner_mid.hip
     for (int i = lane; i < 16 * PKT; i += 64) {
       const int row = i / PKT, k = i - row * PKT;
       if (row0 + row < p.M) *reinterpret_cast<u32x4*>(y + (row0 + row) * p.y_pitch + k * 8) = *reinterpret_cast<const u32x4*>(so + row * OS + k * 8);

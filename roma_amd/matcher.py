@@ -76,6 +76,21 @@ def block_impl(Dp, dtype, B, h, w):
     return "split_small" if Dp <= 32 else "split_gemm"
 
 
+MID_ONE_MIN_PIXELS = 2 * 280 * 280
+
+
+def mid_block_impl(dtype, Dp, B, h, w):
+    """How a `split_mfma` block runs on a (B,h,w) map: "one" (ops.refiner_block_mid, one launch, the intermediate stays on chip) or
+    "two" (ops.dwconv5x5_bn_relu + ops.pointwise_mfma).  Same operands, same bits; the choice is speed alone."""
+    half = dtype in (torch.float16, torch.bfloat16)
+    if not (half and 32 < Dp <= 160):
+        return "two"
+    # one launch where it was measured faster, alternating on one MI355X (tools/mid_micro.py, profiles/refiner_mid_block.md), D = 144,
+    # fp16, B = 2: 52 vs 61 us at 280^2 (700 tiles on 256 workgroups: 2.7 rounds, the partial last round included) and 101 - 109 vs
+    # 129 us at 432^2.  Nothing smaller than 280^2 x 2 was measured, so nothing smaller takes it.
+    return "one" if B * h * w >= MID_ONE_MIN_PIXELS else "two"
+
+
 def project_impl(dtype, channels_last, K, N, out_pitch):
     """Which implementation runs a Decoder.project call: "skinny" (ops.project_skinny, a streaming kernel) for the two finest scales'
     (K, N) on dense channels-last 16-bit feature maps — what the encoder delivers under MIOpen solver search — into rows of a pitch
@@ -105,10 +120,12 @@ class ConvRefiner(nn.Module):
     block (depthwise 5x5 + BN + ReLU + 1x1) is run by the first row that applies (block_impl):
         fp16, Dp == 576, B*ceil(h/8)*ceil(w/16) >= 512   wide         ops.refiner_block_wide, one kernel
         fp16/bf16, Dp <= 32                              fused        ops.refiner_block (kpad 32), one kernel
-        fp16/bf16, 32 < Dp <= 160                        split_mfma   ops.dwconv5x5_bn_relu + ops.pointwise_mfma (kpad 160)
+        fp16/bf16, 32 < Dp <= 160                        split_mfma   B*h*w >= 156 800 (mid_block_impl): ops.refiner_block_mid, one kernel;
+                                                                      smaller maps: ops.dwconv5x5_bn_relu + ops.pointwise_mfma (kpad 160)
         fp32, Dp <= 32                                   split_small  ops.dwconv5x5_bn_relu + ops.pointwise_small (fp32 weights)
         everything else                                  split_gemm   ops.dwconv5x5_bn_relu + a hipBLASLt GEMM (torch.addmm)
-    Measured (`refiner_block_kernel`): fused is 1.8x faster than split at D = 24, 209 vs 121 us at D = 144 (LDS-read bound)."""
+    Measured (DESIGN.md §3, `refiner_block_kernel`): fused is 1.8x faster than split at D = 24, 209 vs 121 us at D = 144 (LDS-read bound);
+    `refiner_mid_kernel`, the two split_mfma kernels joined through LDS, is 101 - 109 vs 129 us there."""
 
     def __init__(self, in_dim, hidden_dim, out_dim, hidden_blocks, displacement_emb_dim, local_corr_radius=None,
                  amp_dtype=torch.float16):
@@ -206,13 +223,17 @@ class ConvRefiner(nn.Module):
             ops.local_correlation(d[:, :C], yy, r, flow=flow, out=d[:, 2 * C + E:D], batch_shift=batch_shift)   # :121-125
         impl = block_impl(Dp, dtype, B, h, w)
         cur = buf
-        nxt = torch.empty_like(buf) if impl in ("wide", "fused") else None    # the one-kernel blocks ping-pong between two buffers
+        mid_one = impl == "split_mfma" and mid_block_impl(dtype, Dp, B, h, w) == "one"
+        nxt = torch.empty_like(buf) if impl in ("wide", "fused") or mid_one else None    # the one-kernel blocks ping-pong between two buffers
         for blk in P.blocks[impl]:                                                             # :139-140
             if impl == "wide":
                 ops.refiner_block_wide(cur, blk.taps, blk.scale, blk.shift, blk.wt_panels, blk.bias, out=nxt)
                 cur, nxt = nxt, cur
             elif impl == "fused":
                 ops.refiner_block(cur, blk.w25, blk.scale, blk.shift, blk.wt_out_in, blk.bias, Dp, out=nxt)
+                cur, nxt = nxt, cur
+            elif mid_one:
+                ops.refiner_block_mid(cur, blk.w25, blk.scale, blk.shift, blk.wt_out_in, blk.bias, Dp, out=nxt)
                 cur, nxt = nxt, cur
             else:
                 t = ops.dwconv5x5_bn_relu(cur.permute(0, 3, 1, 2), blk.w25, blk.scale, blk.shift)

@@ -813,6 +813,24 @@ def refiner_block(x_nhwc, w25, scale, shift, wt, bias, C, out=None):
     return out
 
 
+def refiner_block_mid(x_nhwc, w25, scale, shift, wt, bias, C, out=None):
+    """One ConvRefiner block (matcher.py:77-103) for 32 < C <= 160, fp16/bf16, in one launch, with the operands and the bits of
+    pointwise_mfma(dwconv5x5_bn_relu(x)): x_nhwc (B,h,w,pitch) contiguous; w25 (25,C) fp32 tap-major; scale / shift (C) fp32;
+    wt (160,160) [out][in] in x's dtype and bias (160) fp32, zero-padded.  out must not overlap x; its channels [C, pitch) are not
+    written."""
+    _need_gpu(x_nhwc, w25, scale, shift, wt, bias, out)
+    B, h, w, pitch = x_nhwc.shape
+    assert x_nhwc.is_contiguous() and wt.is_contiguous() and w25.is_contiguous() and wt.dtype == x_nhwc.dtype
+    assert w25.shape == (25, C) and wt.shape == (160, 160) and scale.numel() == shift.numel() == C and bias.numel() == 160
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (w25, scale, shift, bias))
+    if out is None:
+        out = torch.empty_like(x_nhwc)
+    assert out.is_contiguous() and out.shape == x_nhwc.shape and out.dtype == x_nhwc.dtype
+    check(_lib.load().roma_refiner_block_mid(_p(x_nhwc), _p(w25), _p(scale), _p(shift), _p(wt), _p(bias), _p(out), B, C, h, w,
+                                             _dt(x_nhwc), pitch, pitch, _stream()), "roma_refiner_block_mid")
+    return out
+
+
 def refiner_head(x_nhwc, wo, bo, flow, certainty, sx, sy, want_delta=False):
     """out_conv (D -> 3, fp32) of the last refiner block fused with the flow / certainty update (matcher.py:141, 397-402).
     x_nhwc: (B,h,w,pitch) channels-last activation; wo (C,3) fp32; bo (3) fp32; flow (B,2,h,w) fp32 is updated IN PLACE;
