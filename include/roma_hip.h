@@ -466,6 +466,41 @@ int roma_refine_homography(const double* xa, const double* xb, const double* H_i
                            double threshold, int iters, double* H, unsigned char* mask, double* cost, int* count, int* steps,
                            void* stream);
 
+/* Absolute pose from 2D-3D matches (csrc/absolute_pose.hip): RANSAC with a P3P minimal solver, and the non-linear
+ * refinement behind it — what places a further image against the points of roma_triangulate or of a depth map, where a host path
+ * calls cv2.solvePnPRansac or poselib.estimate_absolute_pose.  Convention x ~ K (R X + t).
+ * X: (P,N,3) fp64 world points (any frame); x: (P,N,2) fp64 PIXEL coordinates of the image being placed (16-byte aligned for
+ * roma_absolute_pose_select and roma_refine_absolute_pose); K: (P,3,3) fp64, upper triangular with last row 0 0 1.  `threshold` is in
+ * pixels: a match is an inlier when its squared reprojection error is below threshold^2 and it lies in front of the camera.
+ * `scoring`: 0 = MSAC, 1 = MAGSAC++ (the tables of roma_magsac_table).  `iters` samples of 3 matches per pair, all drawn and scored, up
+ * to 4 poses each; the draw is the hash of the RANSAC block above with stage 5 and p = p0 + pair (absolute_pose.hip pins the solver
+ * and its tolerances).  A row with a non-finite X or x is never sampled and never an inlier; a K with fx * fy == 0 or a non-finite
+ * entry makes every sample of its pair invalid.  The world points are normalised per pair (X' = s (X - c): centroid c, mean distance
+ * sqrt 3), so the fp32 scoring does not depend on where the world's origin is.  The library allocates nothing.
+ *
+ * roma_absolute_pose_workspace: host function; the workspace size in bytes (<0 on bad arguments) and, if offsets != NULL, the byte
+ *   offsets of its 12 regions: [0]-[8] as roma_ransac_workspace with S = 3 and R = 4, where [0] is (c_x, c_y, c_z, s, 0, 0, 0, 0) per
+ *   pair, [1] the scoring records (P,N,4) fp32 = (X'_x, X'_y, X'_z, u), NaN where a match is not usable, and [3] the rotations
+ *   (P,iters,4,3,3) fp64; [9] t' (P,iters,4,3) fp64, the translation in the normalised frame, t = t' / s - R c; [10] v (P,N) fp32 of
+ *   the scoring records; [11] (P,N,5) fp64 = (X', K^-1 x), the solver's copy.
+ * roma_absolute_pose_hypotheses: normalisation, samples, P3P and scoring into the workspace (all regions).
+ * roma_absolute_pose_select: the lowest-cost slot per pair (lowest slot on ties), then lo_iters rounds of local optimisation: one damped
+ *   Gauss-Newton step of roma_refine_absolute_pose on the inliers (weighted by W for MAGSAC++), kept only if the cost drops.
+ *   R: (P,3,3) orthonormal, det +1; t: (P,3); mask: (P,N) uint8.  A pair without a valid slot: R and t all zero, empty mask.
+ * roma_refine_absolute_pose: Levenberg-Marquardt from (R_in, t_in) on the sum over the usable matches (finite, allowed by mask_in —
+ *   (P,N) uint8, NULL = all —, in front of the camera) of min(e, threshold^2), at most `iters` steps over 3 rotation and 3 translation
+ *   parameters; the schedule and the outputs are those of roma_refine_pose.  A pair with fewer than 4 weighted matches, a singular
+ *   normal matrix, an input pose that is not finite, or no step that lowers the cost gets its input pose back bit for bit (steps = 0)
+ *   with its own mask, cost and count.  One launch, no workspace. */
+long roma_absolute_pose_workspace(int P, int N, int iters, long* offsets);
+int roma_absolute_pose_hypotheses(const double* X, const double* x, const double* K, int P, int N, int iters, float threshold,
+                                  int scoring, unsigned seed, int p0, void* ws, long ws_bytes, void* stream);
+int roma_absolute_pose_select(const double* X, const double* x, const double* K, int P, int N, int iters, float threshold, int scoring,
+                              int lo_iters, const void* ws, long ws_bytes, double* R, double* t, unsigned char* mask, void* stream);
+int roma_refine_absolute_pose(const double* X, const double* x, const double* K, const double* R_in, const double* t_in,
+                              const unsigned char* mask_in, int P, int N, double threshold, int iters, double* R, double* t,
+                              unsigned char* mask, double* cost, int* count, int* steps, void* stream);
+
 /* Two-view triangulation of matches under a known relative pose (csrc/triangulate.hip) — what a caller does with
  * the (R, t) of roma_recover_pose / roma_refine_pose: a point cloud of the sampled matches, or a depth map per image from every row of
  * the dense warp.  Convention of roma_recover_pose: x_B ~ K_B (R X_A + t).  Points are expressed in camera A's frame, in units of

@@ -39,6 +39,12 @@ the reference's HPatches benchmark (hpatches_sequences_homog_benchmark.py:80-86)
 `warp_kpts` and `get_gt_warp` are the reference's ground-truth warp from two depth maps and a relative pose (romatch/utils/utils.py:
 326-455; csrc/depth_warp.hip, fp64 per point as there), and `dense_match_metrics` / `geometric_dist` the dense MegaDepth benchmark's
 EPE and PCK@1/3/5 of a warp against it (romatch/benchmarks/megadepth_dense_benchmark.py:17-42), fused into one pass.
+
+`find_absolute_pose`, `refine_absolute_pose` and `estimate_absolute_pose` place a further image against 3-D points (csrc/
+absolute_pose.hip): P3P RANSAC on 2D-3D matches, x ~ K (R X + t), scored by the reprojection error in pixels, and Levenberg-Marquardt
+on the truncated reprojection cost — what a host path calls cv2.solvePnPRansac or poselib.estimate_absolute_pose for.  The points come
+from `triangulate` (camera A's frame, in baselines), from `depth_from_warp`, or from a depth map through `lift_keypoints`;
+`absolute_pose_error` is the metric (camera centre and rotation).
 """
 from __future__ import annotations
 
@@ -899,3 +905,248 @@ def geometric_dist(depth1, depth2, T_1to2, K1, K2, dense_matches):
     n = m.n_valid.sum().to(torch.float32)
     return (m.gd[m.prob == 1], m.n_pck_1.sum().to(torch.float32) / n, m.n_pck_3.sum().to(torch.float32) / n,
             m.n_pck_5.sum().to(torch.float32) / n, m.prob)
+
+
+# ------------------------------------------------------------------------------------------------------------ absolute pose
+CameraPose = RelativePose                 # what estimate_absolute_pose returns: the same R / t / Rt holder, t in world units
+_AP_SLOTS = 4
+_AP_REGIONS = 12
+_AP_RANSAC_OPT = {"max_reproj_error": 12.0, "max_iterations": 1000, "min_inliers": 3, "refine_iterations": 15}
+
+
+def _points3d(X, x):
+    """X (N,3) or (P,N,3), x (N,2) or (P,N,2), fp32/fp64 device tensors -> contiguous (P,N,3), (P,N,2) fp64, single-pair flag"""
+    if X.dim() not in (2, 3) or X.shape[-1] != 3 or x.shape != X.shape[:-1] + (2,):
+        raise ValueError(f"expected world points (N,3) or (P,N,3) and pixels (N,2) or (P,N,2), got {tuple(X.shape)} and {tuple(x.shape)}")
+    for t in (X, x):
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"points must be float32 or float64, got {t.dtype}")
+    single = X.dim() == 2
+    P, N = (1, X.shape[0]) if single else (X.shape[0], X.shape[1])
+    if N < 3:
+        raise ValueError(f"{N} matches, the minimal sample needs 3")
+    if P < 1:
+        raise ValueError("empty batch")
+    _need_gpu(X, x)
+    return X.reshape(P, N, 3).to(torch.float64).contiguous(), x.reshape(P, N, 2).to(torch.float64).contiguous(), single
+
+
+def absolute_pose_workspace_layout(P, N, iters):
+    """(total bytes, [region offsets]) of the workspace of roma_absolute_pose_hypotheses (include/roma_hip.h: 12 regions)"""
+    off = (ctypes.c_long * _AP_REGIONS)()
+    total = _lib.load().roma_absolute_pose_workspace(P, N, iters, ctypes.cast(off, ctypes.c_void_p))
+    if total < 0:
+        check(int(total), "roma_absolute_pose_workspace")
+    return int(total), list(off)
+
+
+def _ap_chunks(P, N, iters):
+    """_chunks for the absolute-pose workspace"""
+    per_pair, _ = absolute_pose_workspace_layout(1, N, iters)
+    most = max(1, _WORKSPACE_LIMIT // per_pair)
+    n = -(-P // most)
+    step = -(-P // n)
+    return [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
+
+
+def _ap_hypotheses(Xc, xc, Kc, threshold, iters, score, seed, p0, ws):
+    check(_lib.load().roma_absolute_pose_hypotheses(Xc.data_ptr(), xc.data_ptr(), Kc.data_ptr(), Xc.shape[0], Xc.shape[1], iters,
+                                                    float(threshold), score, seed, p0, ws.data_ptr(), ws.numel(), _stream()),
+          "roma_absolute_pose_hypotheses")
+
+
+def find_absolute_pose(X, x, K, threshold=2.0, max_iters=1000, seed=None, lo_iters=3, refine_iters=0, *, scoring="msac"):
+    """Camera pose (R, t) with x ~ K (R X + t) from 2D-3D matches, on the device (csrc/absolute_pose.hip): what places a further image
+    against the points of `triangulate`, of `depth_from_warp` or of `lift_keypoints` — the call a host path makes to
+    cv2.solvePnPRansac.  X: world points (N,3) or (P,N,3) in any frame, x: their pixels (N,2) or (P,N,2) in the image being placed,
+    fp32/fp64; K: (3,3) shared or (P,3,3), tensor or numpy, upper triangular with last row 0 0 1.  RANSAC with max_iters P3P samples
+    per pair, all drawn and scored (up to 4 poses each, fp64), the squared reprojection error in pixels scored in fp32 on world points
+    normalised per pair, lowest cost wins, then lo_iters rounds of a damped Gauss-Newton step on the inliers.  A match is an inlier
+    when its reprojection error is below threshold (pixels) and it lies in front of the camera.  Rows with a NaN / inf in X or x are
+    never sampled and never inliers (triangulate's invalid rows can be passed as NaN).  Returns (R fp64 (3,3) or (P,3,3) orthonormal
+    with det +1, t fp64 (3,) or (P,3) in world units, mask bool); R and t all zero and an empty mask when no sample gives a model.
+    refine_iters > 0 polishes the RANSAC pose by refine_absolute_pose on all matches at the same threshold and returns the refined
+    pose's mask; 0, the default, returns the RANSAC pose as it is.  scoring: "msac" or "magsac" (module docstring).
+    At 30 % inliers (1 - 0.3^3)^1000 = 1e-12 of the calls draw no clean sample.  No host synchronisation."""
+    score = _scoring(scoring)
+    refine_iters = _refine_iters(refine_iters)
+    _args(threshold, max_iters, lo_iters)
+    Xw, xp, single = _points3d(X, x)
+    P, N = Xw.shape[0], Xw.shape[1]
+    Kp = _intrinsics(K, P, Xw.device, "K")
+    iters, seed = int(max_iters), _seed(seed)
+    R = torch.empty((P, 3, 3), dtype=torch.float64, device=Xw.device)
+    t = torch.empty((P, 3), dtype=torch.float64, device=Xw.device)
+    mask = torch.empty((P, N), dtype=torch.uint8, device=Xw.device)
+    lib = _lib.load()
+    chunks = _ap_chunks(P, N, iters)
+    # one workspace, sized for the widest chunk, serves every chunk in stream order (a narrower chunk's layout is no larger)
+    total, _ = absolute_pose_workspace_layout(max(b - a for a, b in chunks), N, iters)
+    ws = torch.empty((total,), dtype=torch.uint8, device=Xw.device)
+    for a, b in chunks:
+        Xc, xc, Kc = Xw[a:b], xp[a:b], Kp[a:b]
+        _ap_hypotheses(Xc, xc, Kc, threshold, iters, score, seed, a, ws)
+        check(lib.roma_absolute_pose_select(Xc.data_ptr(), xc.data_ptr(), Kc.data_ptr(), b - a, N, iters, float(threshold), score,
+                                            int(lo_iters), ws.data_ptr(), total, R[a:b].data_ptr(), t[a:b].data_ptr(),
+                                            mask[a:b].data_ptr(), _stream()), "roma_absolute_pose_select")
+    if refine_iters > 0:
+        (R, t, mask), _ = _refine_absolute(R, t, Xw, xp, Kp, threshold, refine_iters, None)
+    else:
+        mask = mask.bool()
+    return (R[0], t[0], mask[0]) if single else (R, t, mask)
+
+
+def _refine_absolute(R, t, Xw, xp, Kp, threshold, iters, m):
+    """roma_refine_absolute_pose on prepared (P,...) tensors -> (R, t, mask bool), (cost, count, steps)"""
+    P, N = Xw.shape[0], Xw.shape[1]
+    dev = Xw.device
+    Ro = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    to = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
+    cost = torch.empty((P,), dtype=torch.float64, device=dev)
+    count = torch.empty((P,), dtype=torch.int32, device=dev)
+    steps = torch.empty((P,), dtype=torch.int32, device=dev)
+    check(_lib.load().roma_refine_absolute_pose(Xw.data_ptr(), xp.data_ptr(), Kp.data_ptr(), R.data_ptr(), t.data_ptr(),
+                                                None if m is None else m.data_ptr(), P, N, float(threshold), int(iters), Ro.data_ptr(),
+                                                to.data_ptr(), out.data_ptr(), cost.data_ptr(), count.data_ptr(), steps.data_ptr(),
+                                                _stream()), "roma_refine_absolute_pose")
+    return (Ro, to, out.bool()), (cost, count, steps)
+
+
+def refine_absolute_pose(R, t, X, x, K, threshold=2.0, iters=15, mask=None, return_info=False):
+    """Non-linear refinement of an absolute pose (R, t) — of find_absolute_pose — on the 2D-3D matches it was estimated from:
+    Levenberg-Marquardt, at most `iters` steps over 3 rotation and 3 translation parameters, on the sum over the matches of
+    min(e, threshold^2), e the squared reprojection error in pixels (what find_absolute_pose scores with).  Matches beyond the
+    threshold, behind the camera or not finite carry no weight, and `mask` (bool / uint8) optionally names the only matches that may
+    carry any.  R (3,3) or (P,3,3), t (3,) or (P,3); X, x, K as find_absolute_pose (at least 4 matches).  Returns (R orthonormal fp64,
+    t fp64, mask bool: e < threshold^2 and in front under the returned pose); with return_info also a dict of device tensors: cost
+    (fp64, the truncated cost of the returned pose), count (int32, its inliers), steps (int32, the steps kept).  A step is kept only
+    if it lowers the cost; a pair that cannot be refined (fewer than 4 weighted matches, a singular normal matrix, a pose that is not
+    finite, no step that lowers the cost) gets its pose back bit for bit, with steps = 0."""
+    _need_gpu(R, t)
+    _refine_args(threshold, iters)
+    Xw, xp, single = _points3d(X, x)
+    P, N = Xw.shape[0], Xw.shape[1]
+    if N < 4:
+        raise ValueError(f"{N} matches, the refinement needs 4")
+    if R.shape != ((3, 3) if single else (P, 3, 3)) or t.shape != ((3,) if single else (P, 3)):
+        raise ValueError(f"R {tuple(R.shape)}, t {tuple(t.shape)} do not match the points {tuple(X.shape)}")
+    Kp = _intrinsics(K, P, Xw.device, "K")
+    r0 = R.reshape(P, 3, 3).to(torch.float64).contiguous()
+    t0 = t.reshape(P, 3).to(torch.float64).contiguous()
+    m = _mask(mask, P, N, x)
+    res, info = _refine_absolute(r0, t0, Xw, xp, Kp, threshold, iters, m)
+    return _refined(res, info, single, return_info)
+
+
+def estimate_absolute_pose(points2D, points3D, camera, ransac_opt=None, *, seed=None, scoring="msac"):
+    """Drop-in for poselib.estimate_absolute_pose on the device: find_absolute_pose -> refine_absolute_pose.  points2D (N,2) or
+    (P,N,2) pixels, points3D (N,3) or (P,N,3) on the device; camera: a dict with model 'PINHOLE' and params [fx, fy, cx, cy] (one
+    camera for the whole batch).  ransac_opt keys:
+      max_reproj_error    pixels, default 12.0 (PoseLib's default)
+      max_iterations      default 1000 samples; there is no early exit, every sample is drawn and scored, so this is the whole budget
+      min_inliers         default 3: a pair whose RANSAC pose has fewer inliers keeps that pose unrefined
+      refine_iterations   default 15 Levenberg-Marquardt steps
+    Any other key, or another camera model, raises ValueError, and so do fewer than 3 matches (as estimate_relative_pose below its
+    minimal sample).  Returns (pose, info): pose.R, pose.t,
+    pose.Rt (CameraPose; x ~ K (R X + t)); info = {inliers: bool mask of the returned pose, num_inliers: int32, model_score: fp64
+    truncated cost, refinements: int32 steps kept — device tensors, nothing is copied to the host —, iterations: max_iterations}."""
+    _scoring(scoring)
+    opt = dict(_AP_RANSAC_OPT)
+    for k, v in (ransac_opt or {}).items():
+        if k not in opt:
+            raise ValueError(f"ransac_opt: unknown key {k!r}; known: {sorted(opt)}")
+        opt[k] = v
+    _, K = _focal(camera, "camera")
+    if not float(opt["max_reproj_error"]) > 0:
+        raise ValueError(f"ransac_opt: max_reproj_error must be positive, got {opt['max_reproj_error']}")
+    if int(opt["max_iterations"]) < 1 or int(opt["min_inliers"]) < 0 or int(opt["refine_iterations"]) < 0:
+        raise ValueError(f"ransac_opt: bad counts {opt}")
+    thr = float(opt["max_reproj_error"])
+    _points3d(points3D, points2D)                                    # shapes, counts and the device, before anything is allocated
+    K = torch.tensor(K, dtype=torch.float64).to(points2D.device)
+    R0, t0, mask0 = find_absolute_pose(points3D, points2D, K, thr, int(opt["max_iterations"]), seed, scoring=scoring)
+    if points2D.shape[-2] < 4:                                       # the refinement needs 4 matches
+        count = mask0.sum(-1).to(torch.int32)
+        info = {"inliers": mask0, "num_inliers": count, "model_score": torch.full_like(count, float("nan"), dtype=torch.float64),
+                "iterations": int(opt["max_iterations"]), "refinements": torch.zeros_like(count)}
+        return CameraPose(R0, t0), info
+    R, t, mask, refined = refine_absolute_pose(R0, t0, points3D, points2D, K, thr, int(opt["refine_iterations"]), return_info=True)
+    cost, count, steps = refined["cost"], refined["count"], refined["steps"]
+    keep = mask0.sum(-1) >= int(opt["min_inliers"])                  # on the device: no host synchronisation
+    R = torch.where(keep[..., None, None], R, R0)
+    t = torch.where(keep[..., None], t, t0)
+    steps = torch.where(keep, steps, torch.zeros_like(steps))
+    info = {"inliers": mask, "num_inliers": count, "model_score": cost, "iterations": int(opt["max_iterations"]), "refinements": steps}
+    return CameraPose(R, t), info
+
+
+def absolute_pose_error(R, t, T_gt):
+    """Error of an absolute pose against T_gt (...,3,4) or (...,4,4) = [R_gt | t_gt] (tensor or numpy), in torch on the device, batched:
+    (e_c, e_R) = the distance between the camera centres -R^T t in world units, and the geodesic angle of R^T R_gt in degrees."""
+    _need_gpu(R, t)
+    T_gt = torch.as_tensor(T_gt).to(device=R.device, dtype=R.dtype)
+    R_gt, t_gt = T_gt[..., :3, :3], T_gt[..., :3, 3]
+    centre = -(R.transpose(-1, -2) @ t.unsqueeze(-1)).squeeze(-1)
+    centre_gt = -(R_gt.transpose(-1, -2) @ t_gt.unsqueeze(-1)).squeeze(-1)
+    e_c = torch.linalg.norm(centre - centre_gt, dim=-1)
+    cos = ((R * R_gt).sum((-1, -2)) - 1.0) / 2.0
+    return e_c, torch.rad2deg(torch.acos(torch.clamp(cos, -1.0, 1.0)).abs())
+
+
+def lift_keypoints(kpts, depth, K):
+    """World points of pixel key-points from a depth map, in that camera's frame: X = depth(kpt) K^-1 (u, v, 1).  kpts (N,2) or (P,N,2)
+    pixels (the centre of the top-left pixel is (0.5, 0.5), as to_pixel_coordinates), depth (H,W) or (P,H,W), K as find_absolute_pose.
+    The depth is sampled nearest-neighbour.  Returns (...,N,3) fp64; a row is NaN where the depth is <= 0 or not finite or the
+    key-point lies outside the map — rows the absolute-pose estimators skip by construction.  torch ops only; not a hot path."""
+    _need_gpu(kpts, depth)
+    if kpts.dim() not in (2, 3) or kpts.shape[-1] != 2 or depth.dim() != kpts.dim() or (kpts.dim() == 3 and depth.shape[0] != kpts.shape[0]):
+        raise ValueError(f"expected key-points (N,2) with depth (H,W), or (P,N,2) with (P,H,W), got {tuple(kpts.shape)} and {tuple(depth.shape)}")
+    single = kpts.dim() == 2
+    kp = kpts.reshape((1,) + tuple(kpts.shape[-2:]) if single else kpts.shape).to(torch.float64)
+    dm = depth.reshape((1,) + tuple(depth.shape[-2:]) if single else depth.shape).to(torch.float64)
+    P, N, (H, W) = kp.shape[0], kp.shape[1], dm.shape[-2:]
+    Ki = _inverse_intrinsics(_intrinsics(K, P, kp.device, "K"))
+    col, row = torch.floor(kp[..., 0]), torch.floor(kp[..., 1])
+    inside = (col >= 0) & (col < W) & (row >= 0) & (row < H)
+    idx = (row.clamp(0, H - 1) * W + col.clamp(0, W - 1)).to(torch.int64)
+    d = torch.gather(dm.reshape(P, H * W), 1, torch.where(inside, idx, torch.zeros_like(idx)))
+    ok = inside & torch.isfinite(d) & (d > 0)
+    rays = torch.cat([kp, torch.ones_like(kp[..., :1])], -1) @ Ki.transpose(-1, -2)
+    X = torch.where(ok[..., None], rays * d[..., None], torch.full_like(rays, float("nan")))
+    return X[0] if single else X
+
+
+def absolute_pose_hypotheses(X, x, K, threshold=2.0, max_iters=1000, seed=0, *, scoring="msac"):
+    """Every hypothesis of one find_absolute_pose call, before selection (batched (P,...) shapes even for a single pair): samples
+    (P,iters,3) int32 (a row of -1 for an invalid sample); R (P,iters,4,3,3), t (P,iters,4,3) fp64 in the WORLD frame (slots in the
+    solver's order, zero where not valid); valid (P,iters,4) bool; cost (P,iters,4) fp64 of the chosen scoring (+inf if invalid);
+    count (P,iters,4) int32 inliers; centroid (P,3), scale (P,) of the normalisation.  Pair p draws what it draws in
+    find_absolute_pose with the same seed.  An inspection helper with score_hypotheses' batch limit."""
+    score = _scoring(scoring)
+    _args(threshold, max_iters, 0)
+    Xw, xp, _ = _points3d(X, x)
+    P, N, iters = Xw.shape[0], Xw.shape[1], int(max_iters)
+    Kp = _intrinsics(K, P, Xw.device, "K")
+    total, off = absolute_pose_workspace_layout(P, N, iters)
+    if total > _WORKSPACE_LIMIT:
+        raise ValueError(f"absolute_pose_hypotheses: {P} pairs need a {total >> 20} MiB workspace, over the {_WORKSPACE_LIMIT >> 20} MiB "
+                         "limit; call it on fewer pairs")
+    ws = torch.empty((total,), dtype=torch.uint8, device=Xw.device)
+    _ap_hypotheses(Xw, xp, Kp, threshold, iters, score, _seed(seed), 0, ws)
+    norm = _view(ws, off, 0, torch.float64, (P, 8))
+    c, s = norm[:, :3].clone(), norm[:, 3].clone()
+    R = _view(ws, off, 3, torch.float64, (P, iters, _AP_SLOTS, 3, 3)).clone()
+    tn = _view(ws, off, 9, torch.float64, (P, iters, _AP_SLOTS, 3))
+    valid = _view(ws, off, 4, torch.int32, (P, iters, _AP_SLOTS)) != 0
+    t = tn / s[:, None, None, None] - (R @ c[:, None, None, :, None]).squeeze(-1)
+    return {
+        "samples": _view(ws, off, 2, torch.int32, (P, iters, 3)).clone(),
+        "R": R,
+        "t": torch.where(valid[..., None], t, torch.zeros_like(t)),
+        "valid": valid,
+        "cost": _view(ws, off, 7, torch.float64, (P, iters, _AP_SLOTS)).clone(),
+        "count": _view(ws, off, 8, torch.int32, (P, iters, _AP_SLOTS)).clone(),
+        "centroid": c,
+        "scale": s,
+    }
