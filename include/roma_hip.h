@@ -528,6 +528,41 @@ int roma_triangulate(const float* m, const float* to_px, const double* Ka, const
                      const unsigned char* mask_in, int P, int N, int method, float max_reproj, float max_cos_parallax, float* points,
                      float* depth_a, float* depth_b, float* reproj, float* cos_parallax, unsigned char* valid, void* stream);
 
+/* N-view triangulation (csrc/triangulate_nview.hip): a point seen in V posed views, triangulated from all of them, with
+ * the views that disagree left out — a cloud of tracks after the absolute-pose calls above, or ONE depth map of a reference image from
+ * its k warps against k others.  Convention of the absolute-pose calls: x_v ~ K_v (R_v X + t_v), v = 0 .. V-1, 2 <= V <= 32.  ONE
+ * reconstruction per call: there is no P dimension, the views are the batch.
+ *   obs: V device pointers in HOST memory, read during the call.  The observations are read in place: with n = r * row_len + c, r <
+ *     rows, c < row_len, point n of view v is the two fp32 at obs[v] + r * row_stride + c * point_stride (strides in floats, common to
+ *     all views).  Packed (V,N,2): rows = 1, row_len = N, point_stride = 2.  The A half of a symmetric warp (H,2W,4): rows = H,
+ *     row_len = W, row_stride = 8 W, point_stride = 4, the base offset by 2 floats for the predicted x_B and by 0 for the grid of A.
+ *     Pointers 8-byte aligned; strides even, row_stride >= 0, point_stride >= 2; rows <= 65535, rows * row_len <= 2^28;
+ *   to_px: V x 4 floats in HOST memory, (sx, ox, sy, oy) per view, pixel = s * c + o, or NULL: the coordinates are pixels already;
+ *   visible: NULL, or V device pointers in HOST memory to uint8 (rows, row_len) with row stride vis_row_stride (bytes), non-zero =
+ *     view v may see point n; a single entry may be NULL (always visible).  An observation that is not finite is not observed;
+ *   K, R: (V,3,3) fp64 device, K upper triangular with last row 0 0 1; t: (V,3) fp64 device.  A view whose K is singular or whose
+ *     pose is not finite observes nothing;
+ *   max_view_error: pixels, +inf = use every observed view.  Otherwise (robust): every pair of observed views gives the midpoint of its
+ *     two rays; a view is an inlier of it with positive depth and a pixel error <= max_view_error; a hypothesis counts if its own two
+ *     views are inliers and scores sum over observed views of (inlier ? e^2 : max_view_error^2); the lowest score wins, the first pair
+ *     (a, b), a < b, on a tie; the point's view set is the winner's inliers (empty without a hypothesis that counts);
+ *   iters: 0 .. 10 Levenberg-Marquardt steps on the sum over the set of the squared pixel error, from the point closest to the set's
+ *     rays; a step is kept only if the cost drops.  min_views: 2 .. V.  ref_view: the view whose z `depth` reports.
+ * Per call, in fp64: K_v^-1, the centres C_v = -R_v^T t_v and their mean c0 over the usable views in view order; everything per point
+ * is fp32 relative to c0 (the result does not depend on where the world's origin is), and c0 is added back in fp64.
+ * Outputs, device, each may be NULL but not all: points (N,3) fp32, world frame; depth (N) fp32; reproj (N) fp32 = the root of the
+ * MEAN over the used views of the squared pixel error (roma_triangulate reports the root of the SUM over its two images);
+ * cos_parallax (N) fp32 = the smallest cosine over pairs of used views between the rays from the point to their centres; views (N)
+ * uint32, bit v = view v used; valid (N) uint8 = at least min_views used, everything finite, positive depth in every used view,
+ * reproj <= max_reproj, cos_parallax <= max_cos_parallax.  Every requested element is written: exact zeros (views = 0) for a point
+ * with fewer than two views in its set or without a finite solution, the computed values for any other, valid or not; never NaN or
+ * inf.  An output does not depend on which others are requested.  One launch, no workspace, no atomics, no host synchronisation. */
+int roma_triangulate_nview(const float* const* obs, const float* to_px, const unsigned char* const* visible, long vis_row_stride,
+                           const double* K, const double* R, const double* t, int V, int rows, int row_len, long row_stride,
+                           long point_stride, float max_view_error, int iters, int min_views, int ref_view, float max_reproj,
+                           float max_cos_parallax, float* points, float* depth, float* reproj, float* cos_parallax, unsigned* views,
+                           unsigned char* valid, void* stream);
+
 /* Ground-truth warp of key-points from two depth maps and a relative pose (csrc/depth_warp.hip): warp_kpts of the
  * reference (romatch/utils/utils.py:358-455; get_gt_warp is this on the pixel grid).  Convention: X_B = R X_A + t, T = [R | t].
  *   x: (P,N,·) fp32 device, 8-byte aligned, normalised key-points of image A in columns 0-1 of rows `x_stride` floats apart: 2 for

@@ -45,6 +45,11 @@ absolute_pose.hip): P3P RANSAC on 2D-3D matches, x ~ K (R X + t), scored by the 
 on the truncated reprojection cost — what a host path calls cv2.solvePnPRansac or poselib.estimate_absolute_pose for.  The points come
 from `triangulate` (camera A's frame, in baselines), from `depth_from_warp`, or from a depth map through `lift_keypoints`;
 `absolute_pose_error` is the metric (camera centre and rotation).
+
+`triangulate_nview` triangulates tracks seen in V posed views from all of them, leaving out the views that disagree (csrc/
+triangulate_nview.hip: fp32 per point, relative to the mean camera centre, from view constants prepared in fp64; a pairwise robust
+choice of the views, the point closest to their rays, Levenberg-Marquardt on the pixel error), and `depth_from_warps` runs it on the k
+warps of one image against k others, read in place: one depth map of that image from all of them.
 """
 from __future__ import annotations
 
@@ -733,6 +738,221 @@ def depth_from_warp(warp, certainty, R, t, K_A, K_B, H_A, W_A, H_B=None, W_B=Non
     W = W2 // 2 if symmetric else W2
     res = (da[..., :W], valid[..., :W], db[..., W:] if symmetric else None, valid[..., W:] if symmetric else None, points, valid)
     return WarpDepth(*((None if o is None else o[0]) for o in res) if single else res)
+
+
+# ------------------------------------------------------------------------------------------------------ N-view triangulation
+_MAX_VIEWS = 32
+
+
+class MultiViewTriangulation:
+    """What triangulate_nview returns, (N,) device tensors: points (N,3) fp32 in the world frame, depth (the z in view ref_view),
+    reproj_error (pixels, the root of the MEAN over the used views of the squared error), cos_parallax — fp32 —, views (int32 holding
+    the bit pattern of the views used: view v took part where (views >> v) & 1), num_views (uint8, their number), valid (bool)."""
+    __slots__ = ("points", "depth", "reproj_error", "cos_parallax", "views", "num_views", "valid")
+
+    def __init__(self, points, depth, reproj_error, cos_parallax, views, num_views, valid):
+        self.points, self.depth, self.reproj_error, self.cos_parallax = points, depth, reproj_error, cos_parallax
+        self.views, self.num_views, self.valid = views, num_views, valid
+
+    def __repr__(self):
+        return f"MultiViewTriangulation(points={tuple(self.points.shape)}, device={self.points.device})"
+
+
+class MultiViewDepth:
+    """What depth_from_warps returns: depth_A (H,W) fp32, 0 where not valid, valid_A (H,W) bool, num_views (H,W) uint8 (image A
+    counts), reproj_error (H,W) fp32 and points (H,W,3) fp32 in camera A's frame."""
+    __slots__ = ("depth_A", "valid_A", "num_views", "reproj_error", "points")
+
+    def __init__(self, depth_A, valid_A, num_views, reproj_error, points):
+        self.depth_A, self.valid_A, self.num_views, self.reproj_error, self.points = depth_A, valid_A, num_views, reproj_error, points
+
+    def __repr__(self):
+        return f"MultiViewDepth(depth_A={tuple(self.depth_A.shape)}, device={self.depth_A.device})"
+
+
+def _nview_gates(max_view_error, iters, min_views, max_reproj_error, min_parallax_deg, ref_view):
+    """-> (max_view_error or inf, iters, min_views, max_reproj, max_cos_parallax, ref_view), checked before anything looks at a tensor"""
+    view_error = float("inf") if max_view_error is None else float(max_view_error)
+    if not view_error > 0:
+        raise ValueError(f"max_view_error must be positive pixels or None, got {max_view_error}")
+    if not 0 <= int(iters) <= 10:
+        raise ValueError(f"iters must be in [0, 10], got {iters}")
+    if not 2 <= int(min_views) <= _MAX_VIEWS:
+        raise ValueError(f"min_views must be at least 2 and at most the number of views, got {min_views}")
+    if int(ref_view) < 0:
+        raise ValueError(f"ref_view must be a view index, got {ref_view}")
+    _, max_reproj, max_cos = _gates("midpoint", max_reproj_error, min_parallax_deg)
+    return view_error, int(iters), int(min_views), max_reproj, max_cos, int(ref_view)
+
+
+def _popcount(views):
+    """the number of set bits of an int32 bit pattern, uint8"""
+    x = views.to(torch.int64) & 0xFFFFFFFF
+    x = x - ((x >> 1) & 0x55555555)
+    x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+    x = (x + (x >> 4)) & 0x0F0F0F0F
+    return (((x * 0x01010101) >> 24) & 0xFF).to(torch.uint8)
+
+
+def _triangulate_nview(obs, to_px, vis, vis_stride, K, R, t, rows, row_len, row_stride, point_stride, gates, device, keep):
+    """roma_triangulate_nview on V observation pointers (ints) and optional visibility pointers (ints or None); `keep` holds the tensors
+    behind them.  -> points (N,3), depth, reproj, cos_parallax fp32, views int32, valid bool, N = rows * row_len"""
+    V = len(obs)
+    view_error, iters, min_views, max_reproj, max_cos, ref_view = gates
+    if not 2 <= V <= _MAX_VIEWS:
+        raise ValueError(f"{V} views: 2 to {_MAX_VIEWS} are supported")
+    if min_views > V or ref_view >= V:
+        raise ValueError(f"min_views {min_views} and ref_view {ref_view} do not fit {V} views")
+    N = rows * row_len
+    f32 = dict(dtype=torch.float32, device=device)
+    points, depth, reproj, cosp = torch.empty((N, 3), **f32), torch.empty((N,), **f32), torch.empty((N,), **f32), torch.empty((N,), **f32)
+    views = torch.empty((N,), dtype=torch.int32, device=device)
+    valid = torch.empty((N,), dtype=torch.uint8, device=device)
+    obs_tab = (ctypes.c_void_p * V)(*obs)
+    px_tab = None if to_px is None else (ctypes.c_float * (4 * V))(*[float(s) for row in to_px for s in row])
+    vis_tab = None if vis is None else (ctypes.c_void_p * V)(*vis)
+    check(_lib.load().roma_triangulate_nview(ctypes.cast(obs_tab, ctypes.c_void_p), None if px_tab is None else ctypes.cast(px_tab, ctypes.c_void_p),
+                                             None if vis_tab is None else ctypes.cast(vis_tab, ctypes.c_void_p), int(vis_stride),
+                                             K.data_ptr(), R.data_ptr(), t.data_ptr(), V, rows, row_len, int(row_stride), int(point_stride),
+                                             view_error, iters, min_views, ref_view, max_reproj, max_cos, points.data_ptr(), depth.data_ptr(),
+                                             reproj.data_ptr(), cosp.data_ptr(), views.data_ptr(), valid.data_ptr(), _stream()),
+          "roma_triangulate_nview")
+    del keep                                                  # alive until the launch is queued; the stream orders the rest
+    return points, depth, reproj, cosp, views, valid.bool()
+
+
+def _poses(R, t, V, device):
+    """(V,3,3), (V,3), tensors or numpy -> contiguous fp64 on the device"""
+    if not torch.is_tensor(R):
+        R = torch.as_tensor(R, dtype=torch.float64).to(device)
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(t, dtype=torch.float64).to(device)
+    _need_gpu(R, t)
+    if R.shape != (V, 3, 3) or t.shape != (V, 3):
+        raise ValueError(f"R {tuple(R.shape)}, t {tuple(t.shape)}: expected ({V},3,3) and ({V},3)")
+    return R.to(torch.float64).contiguous(), t.to(torch.float64).contiguous()
+
+
+def triangulate_nview(x, R, t, K, *, visible=None, max_view_error=None, iters=3, min_views=2, max_reproj_error=None, min_parallax_deg=0.0,
+                      ref_view=0):
+    """3-D points of tracks seen in V posed views (2 <= V <= 32), each triangulated from all the views that see it, with the views that
+    disagree left out (csrc/triangulate_nview.hip) — what follows find_absolute_pose once a third camera is placed.  Convention of
+    find_absolute_pose: x_v ~ K_v (R_v X + t_v); the points come out in the frame the poses are expressed in (camera A's, when view 0
+    is the identity and the others come from estimate_pose / find_absolute_pose against triangulate's cloud).  One reconstruction per
+    call: the views are the batch.
+    x: (V,N,2) pixels, any float dtype on the device, NaN (or anything not finite) where a view does not see a point; visible: (V,N)
+    bool / uint8, optional, the same as NaN where 0.  R (V,3,3), t (V,3); K (3,3) shared or (V,3,3).  A view with a singular K or a
+    pose that is not finite sees nothing.
+    max_view_error None: every observing view is used.  A number of pixels (robust mode): every pair of observing views proposes the
+    midpoint of its two rays, a view agrees with positive depth and an error within max_view_error, the proposal whose own two views
+    agree and whose truncated squared error over all views is lowest wins (the first pair on a tie), and the views that agree with it
+    are used.  Then the point closest to the rays of the used views, polished by `iters` (0 to 10) Levenberg-Marquardt steps on the
+    squared pixel error; a step is kept only if the error drops.
+    Returns a MultiViewTriangulation: points (N,3), depth (z in view ref_view), reproj_error (root of the MEAN squared pixel error
+    over the used views — triangulate reports the root of the SUM over its two), cos_parallax (the smallest cosine between the rays of
+    two used views at the point: the largest triangulation angle) fp32; views int32, bit v set where view v was used, (views >> v) & 1;
+    num_views uint8; valid bool: at least min_views views used, finite, in front of every used view, reproj_error <=
+    max_reproj_error (None = no gate), parallax >= min_parallax_deg.  A point with fewer than two usable views or no finite solution
+    gets zeros in every field; the others their values, valid or not.  The kernel computes in fp32 relative to the mean of the camera
+    centres (prepared in fp64), so the result does not depend on where the world's origin is.  No host synchronisation: the call can
+    be captured in a hipGraph."""
+    gates = _nview_gates(max_view_error, iters, min_views, max_reproj_error, min_parallax_deg, ref_view)
+    _need_gpu(x, visible)
+    if x.dim() != 3 or x.shape[-1] != 2 or not x.is_floating_point():
+        raise ValueError(f"expected floating-point observations (V,N,2), got {tuple(x.shape)} {x.dtype}")
+    V, N = x.shape[0], x.shape[1]
+    if N < 1:
+        raise ValueError("no points")
+    if visible is not None and visible.shape != (V, N):
+        raise ValueError(f"visible {tuple(visible.shape)} does not match the observations {tuple(x.shape)}")
+    xs = x.to(torch.float32).contiguous()
+    vis = None if visible is None else visible.to(torch.uint8).contiguous()
+    Rp, tp = _poses(R, t, V, x.device)
+    Kp = _intrinsics(K, V, x.device, "K")
+    obs = [xs.data_ptr() + 8 * N * v for v in range(V)]
+    vp = None if vis is None else [vis.data_ptr() + N * v for v in range(V)]
+    points, depth, reproj, cosp, views, valid = _triangulate_nview(obs, None, vp, N, Kp, Rp, tp, 1, N, 0, 2, gates, x.device, (xs, vis))
+    return MultiViewTriangulation(points, depth, reproj, cosp, views, _popcount(views), valid)
+
+
+def depth_from_warps(warps, certainties, R, t, K_A, K, H_A, W_A, sizes=None, *, certainty_thresh=0.05, masks=None, symmetric=True,
+                     max_view_error=None, iters=3, min_views=2, max_reproj_error=None, min_parallax_deg=0.0):
+    """ONE depth map of image A from its k warps against k other images B_1 .. B_k (k <= 31) and their poses: every pixel of A is a
+    track seen by A at its grid position and by each B_v at the warp's prediction, triangulated by triangulate_nview's kernel in one
+    launch — views that disagree can be left out (max_view_error), and short baselines are backed by long ones.
+    warps: a list or tuple of k warps of match(A, B_v), (H,2W,4) each — the left half rows are [grid_A, predicted x_Bv] —, or (H,W,4)
+    each with symmetric=False, in normalised coordinates; or one (k,H,2W,4) tensor.  They are read in place: fp32 warps of one
+    common layout whose last dimension is dense (stride 1), with even row and point strides and an 8-byte aligned address — what
+    match() returns, a slice of match_tensors or of a stack of them; anything else is refused (make it .float().contiguous()).
+    certainties: the k certainty maps, (H,2W) (or (H,W)) each, or one (k,...) tensor; masks: optional, the same shapes.  View v sees
+    a pixel where certainty_v > certainty_thresh and mask_v is set.
+    View 0 is A itself, observed at its grid (columns 0:2 of the first warp), always visible, with the identity pose and K_A at H_A x
+    W_A.  Views 1 .. k are the B_v with R[v-1], t[v-1] such that x_Bv ~ K[v-1] (R[v-1] X_A + t[v-1]); R (k,3,3), t (k,3), K (3,3)
+    shared or (k,3,3); sizes: k pairs (H_Bv, W_Bv), default (H_A, W_A) for all.
+    THE k POSES MUST SHARE ONE SCALE.  k results of estimate_pose do not: each has a unit baseline of its own.  Take estimate_pose for
+    B_1, triangulate its matches, and place B_2, ... against that cloud with find_absolute_pose: those poses do.
+    max_view_error, iters, min_views (A counts), max_reproj_error, min_parallax_deg as triangulate_nview.
+    Returns a MultiViewDepth: depth_A (H,W) = z in camera A, 0 where not valid, valid_A, num_views, reproj_error and points (H,W,3)
+    in A's frame.  The B-side depth maps are not computed.  No host synchronisation."""
+    gates = _nview_gates(max_view_error, iters, min_views, max_reproj_error, min_parallax_deg, 0)
+    thresh = float(certainty_thresh)
+
+    def listed(v, name):
+        if torch.is_tensor(v):
+            _need_gpu(v)
+            return [v[i] for i in range(v.shape[0])]
+        if not isinstance(v, (list, tuple)) or len(v) < 1:
+            raise ValueError(f"{name}: expected a list or tuple of tensors, or one stacked tensor")
+        _need_gpu(*v)
+        return list(v)
+
+    ws, cs = listed(warps, "warps"), listed(certainties, "certainties")
+    ms = None if masks is None else listed(masks, "masks")
+    k = len(ws)
+    if not 1 <= k <= _MAX_VIEWS - 1:
+        raise ValueError(f"{k} warps: 1 to {_MAX_VIEWS - 1} are supported")
+    if len(cs) != k or (ms is not None and len(ms) != k):
+        raise ValueError(f"{k} warps need {k} certainties (and masks), got {len(cs)}" + ("" if ms is None else f" and {len(ms)}"))
+    w0 = ws[0]
+    if w0.dim() != 3 or w0.shape[-1] != 4:
+        raise ValueError(f"expected warps (H, W2, 4), got {tuple(w0.shape)}")
+    H, W2 = w0.shape[0], w0.shape[1]
+    if symmetric and W2 % 2:
+        raise ValueError(f"a symmetric warp has an even width, got {W2}; pass symmetric=False for (H, W, 4) warps")
+    W = W2 // 2 if symmetric else W2
+    for i, w in enumerate(ws):
+        if w.shape != w0.shape or w.dtype != torch.float32 or w.device != w0.device:
+            raise ValueError(f"warp {i}: expected float32 {tuple(w0.shape)} on {w0.device}, got {w.dtype} {tuple(w.shape)} on {w.device}")
+        if w.stride() != w0.stride() or w.stride(2) != 1 or w.stride(0) % 2 or w.stride(1) % 2 or w.stride(0) < 0 or w.stride(1) < 2 \
+                or w.data_ptr() % 8:
+            raise ValueError(f"warp {i}: strides {w.stride()} at address % 8 = {w.data_ptr() % 8} cannot be read in place (one common layout, "
+                             "last dimension dense, even strides, 8-byte aligned); pass .contiguous() warps")
+    for name, vs in (("certainty", cs), ("mask", ms)):
+        for i, v in enumerate(vs or ()):
+            if v.shape != (H, W2):
+                raise ValueError(f"{name} {i} {tuple(v.shape)} does not match the warps {tuple(w0.shape)}")
+    sizes = [(H_A, W_A)] * k if sizes is None else [tuple(s) for s in sizes]
+    if len(sizes) != k:
+        raise ValueError(f"sizes: expected {k} pairs (H_B, W_B), got {len(sizes)}")
+    dev = w0.device
+    Rk, tk = _poses(R, t, k, dev)
+    Rp = torch.cat([torch.eye(3, dtype=torch.float64, device=dev)[None], Rk])
+    tp = torch.cat([torch.zeros((1, 3), dtype=torch.float64, device=dev), tk])
+    Kp = torch.cat([_intrinsics(K_A, 1, dev, "K_A"), _intrinsics(K, k, dev, "K")])
+    keep = []
+    for i in range(k):
+        v = cs[i][:, :W] > thresh
+        if ms is not None:
+            v = v & (ms[i][:, :W] != 0)
+        keep.append(v.to(torch.uint8).contiguous())
+    obs = [w0.data_ptr()] + [w.data_ptr() + 8 for w in ws]
+    vis = [None] + [v.data_ptr() for v in keep]
+    to_px = [(W_A / 2, W_A / 2, H_A / 2, H_A / 2)] + [(wb / 2, wb / 2, hb / 2, hb / 2) for hb, wb in sizes]
+    points, depth, reproj, _, views, valid = _triangulate_nview(obs, to_px, vis, W, Kp, Rp, tp, H, W, w0.stride(0), w0.stride(1), gates, dev,
+                                                                (ws, keep))
+    valid = valid.reshape(H, W)
+    return MultiViewDepth(torch.where(valid, depth.reshape(H, W), 0.0), valid, _popcount(views).reshape(H, W), reproj.reshape(H, W),
+                          points.reshape(H, W, 3))
 
 
 # ------------------------------------------------------------------------------------- ground-truth warp from depth, dense metrics
