@@ -240,6 +240,23 @@ int roma_bias_relu_pool2_nchw(void* x, const void* bias, void* pooled, int B, in
 int roma_bias_relu_nhwc(void* x, const void* bias, long npix, int C, int dtype, void* stream);
 int roma_bias_relu_pool2_nhwc(void* x, const void* bias, void* pooled, int B, int C, int H, int W, int dtype, void* stream);
 
+/* MaxPool2d(2, 2) alone on a channels-last map: pooled (B, H/2, W/2, C) = max of each 2x2 block of x (B, H, W, C); H and W even, C a
+ * multiple of 8 (16-bit) / 4 (fp32).  For a layer whose convolution already stored bias + ReLU (roma_conv3x3_bias_relu); on the same
+ * map the result has the bits of roma_bias_relu_pool2_nhwc's pooled output. */
+int roma_maxpool2_nhwc(const void* x, void* pooled, int B, int C, int H, int W, int dtype, void* stream);
+
+/* One VGG19-BN layer in one kernel — encoders.py:68-78 (conv -> BN -> ReLU) with BatchNorm folded into w and bias:
+ *   y[b,h,w,k] = max(round16(sum_{r,s,c} x[b,h+r-1,w+s-1,c] * w[k,r,s,c]) + bias[k], 0), 3x3, stride 1, zero pad 1, fp32 accumulation.
+ * x: (B,H,W) pixels of Cin channels, x_pitch elements apart; w: (Cout,3,3,Cin) dense; bias: (Cout); y: (B,H,W) pixels of Cout channels,
+ * y_pitch apart (channels past Cout of a wider row are left untouched).  dtype ROMA_F16 only (others: ROMA_E_UNSUPPORTED).  Cin, Cout
+ * and the pitches multiples of 8, every buffer 16-byte aligned, each map below 2^31 elements.  The convolution is a Composable
+ * Kernel grouped-forward-convolution instance with the epilogue as its CDE functor; `instance` in [0, count) selects the tile
+ * configuration and ROMA_E_UNSUPPORTED is returned if that instance cannot run the shape.  Nothing is searched or timed. */
+int roma_conv3x3_bias_relu(const void* x, const void* w, const void* bias, void* y, int B, int Cin, int Cout, int H, int W, int dtype,
+                           int x_pitch, int y_pitch, int instance, void* stream);
+/*   Returns the number of instances; with name != NULL also writes instance `index`'s CK type string (at most cap - 1 characters). */
+int roma_conv3x3_bias_relu_instances(int index, char* name, int cap);
+
 /* ConvRefiner block front half — matcher.py:77-103 (create_block: depthwise 5x5 conv, BatchNorm(eval), ReLU),
  * fused, channels-last.  BN is folded by the caller: y = relu(dwconv(x, w) * scale + shift).
  *   x,y: (B,H,W,pitch) `dtype`; w: (25, C) fp32 tap-major; scale, shift: (C) fp32. */

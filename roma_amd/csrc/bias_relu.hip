@@ -138,6 +138,34 @@ __global__ __launch_bounds__(256) void bias_relu_pool_nhwc_kernel(T* __restrict_
   }
 }
 
+// the 2x2 / stride-2 max alone, for a layer whose convolution already stored bias + ReLU (vgg_conv.hip): the map is read once and a
+// quarter of it written; one thread = one channel packet of one POOLED pixel.  The max of rounded values is itself one of them, so
+// the result has the bits bias_relu_pool_nhwc_kernel gives on the same map.
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool2_nhwc_kernel(const T* __restrict__ x, T* __restrict__ pooled, int B, int H, int W, int cpack) {
+  constexpr int E = ElemTraits<T>::kPer16B;
+  const int Ho = H / 2, Wo = W / 2;
+  const long n = (long)B * Ho * Wo * cpack;
+  const u32x4* xv = reinterpret_cast<const u32x4*>(x);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int cp = (int)(i % cpack);
+    long r = i / cpack;
+    const int xo = (int)(r % Wo);
+    r /= Wo;
+    const int yo = (int)(r % Ho), b = (int)(r / Ho);
+    const long idx = (((long)b * H + 2 * yo) * W + 2 * xo) * cpack + cp;
+    float m[E], f[E];
+    unpack16<T>(xv[idx], m);
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+      unpack16<T>(xv[idx + ((k >> 1) * (long)W + (k & 1)) * cpack], f);
+#pragma unroll
+      for (int e = 0; e < E; ++e) m[e] = fmaxf(m[e], f[e]);
+    }
+    reinterpret_cast<u32x4*>(pooled)[i] = pack16<T>(m);
+  }
+}
+
 }  // namespace
 }  // namespace roma
 
@@ -174,6 +202,24 @@ extern "C" int roma_bias_relu_pool2_nhwc(void* x, const void* bias, void* pooled
     case ROMA_F16: hipLaunchKernelGGL((bias_relu_pool_nhwc_kernel<half_t>), dim3(grid), dim3(256), 0, s, (half_t*)x, (const half_t*)bias, (half_t*)pooled, B, H, W, C / e16); break;
     case ROMA_BF16: hipLaunchKernelGGL((bias_relu_pool_nhwc_kernel<bf16_t>), dim3(grid), dim3(256), 0, s, (bf16_t*)x, (const bf16_t*)bias, (bf16_t*)pooled, B, H, W, C / e16); break;
     default: ROMA_REQUIRE(false, ROMA_E_DTYPE, "roma_bias_relu_pool2_nhwc: dtype %d", dtype);
+  }
+  ROMA_CHECK_LAUNCH();
+}
+
+extern "C" int roma_maxpool2_nhwc(const void* x, void* pooled, int B, int C, int H, int W, int dtype, void* stream) {
+  ROMA_REQUIRE(x && pooled, ROMA_E_ARG, "roma_maxpool2_nhwc: null pointer");
+  ROMA_REQUIRE(dtype >= ROMA_F32 && dtype <= ROMA_BF16, ROMA_E_DTYPE, "roma_maxpool2_nhwc: dtype %d", dtype);
+  const int e16 = dtype == ROMA_F32 ? 4 : 8;
+  ROMA_REQUIRE(B > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, ROMA_E_SHAPE, "roma_maxpool2_nhwc: bad shape B=%d H=%d W=%d (even H, W)", B, H, W);
+  ROMA_REQUIRE(C > 0 && C % e16 == 0 && aligned16(x) && aligned16(pooled), ROMA_E_ALIGN,
+               "roma_maxpool2_nhwc: C = %d must be a multiple of %d and the buffers 16-byte aligned", C, e16);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long n = (long)B * (H / 2) * (W / 2) * (C / e16);
+  const unsigned grid = (unsigned)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
+  switch (dtype) {
+    case ROMA_F32: hipLaunchKernelGGL((maxpool2_nhwc_kernel<float>), dim3(grid), dim3(256), 0, s, (const float*)x, (float*)pooled, B, H, W, C / e16); break;
+    case ROMA_F16: hipLaunchKernelGGL((maxpool2_nhwc_kernel<half_t>), dim3(grid), dim3(256), 0, s, (const half_t*)x, (half_t*)pooled, B, H, W, C / e16); break;
+    default: hipLaunchKernelGGL((maxpool2_nhwc_kernel<bf16_t>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)pooled, B, H, W, C / e16); break;
   }
   ROMA_CHECK_LAUNCH();
 }

@@ -21,6 +21,33 @@ def _ver(t):
     return 0 if t.is_inference() else t._version
 
 
+# (Cin, Cout) -> ((fewest pixels B*H*W, most pixels, instance of ops.conv3x3_instances()), ...): the layers of the 560^2 and 864^2
+# pyramids at B = 2 where the fused kernel measured faster than F.conv2d (solver search on) + ops.bias_relu_ by more than the
+# measurement's own spread (tools/vgg_conv_tune.py, profiles/vgg_conv_fused.md).  A range joins the two measured sizes of a layer
+# where both take the same instance; everything else is a single measured size.
+VGG_CONV_TABLE = {
+    (64, 64): ((627200, 1492992, 6),),                          # conv1_2: 122 -> 112 us at 560^2 (with the pool), 292 -> 275 us at 864^2
+    (64, 128): ((156800, 156800, 2), (373248, 373248, 1)),      # conv2_1: 57 -> 44 us, 107 -> 85 us
+    (128, 128): ((156800, 156800, 8), (373248, 373248, 1)),     # conv2_2: 90 -> 81 us, 179 -> 167 us (with the pool)
+    (128, 256): ((39200, 39200, 2), (93312, 93312, 1)),         # conv3_1: 49 -> 42 us, 91 -> 79 us
+    (256, 256): ((93312, 93312, 8),),                           # conv3_2..4: 162 -> 144 us at 216^2; at 140^2 the pooled layer did not win
+    (256, 512): ((9800, 23328, 8),),                            # conv4_1: 55 -> 45 us, 87 -> 77 us
+    (512, 512): ((9800, 23328, 8),),                            # conv4_2..4: 98 -> 78 us, 157 -> 140 us
+}
+
+
+def vgg_conv_impl(dtype, nhwc, Cin, Cout, B, H, W):
+    """Which implementation runs a VGG19 3x3 layer: "library" (F.conv2d + ops.bias_relu_ / ops.bias_relu_pool2_) or the index of the
+    ops.conv3x3_bias_relu instance that measured faster at this size.  Static: no search at run time, so two processes run the same
+    kernels.  fp32, bf16, planar maps, the stem (Cin = 3) and every unmeasured size stay with the library."""
+    if dtype != torch.float16 or not nhwc:
+        return "library"
+    for lo, hi, instance in VGG_CONV_TABLE.get((Cin, Cout), ()):
+        if lo <= B * H * W <= hi:
+            return instance
+    return "library"
+
+
 class VGG19(nn.Module):
     """Parameters live in `layers.{0..39}` exactly like torchvision's vgg19_bn().features[:40] (encoders.py:64)."""
 
@@ -35,6 +62,7 @@ class VGG19(nn.Module):
                 c = v
         self.layers = nn.ModuleList(layers[:40])
         self._folded = None
+        self.conv_impl = vgg_conv_impl                            # (dtype, nhwc, Cin, Cout, B, H, W) -> "library" | instance index
 
     def fold(self, dtype, nhwc=False):
         """conv+BN(eval) -> one conv: w' = w*g/sqrt(var+eps), b' = (b-mean)*g/sqrt(var+eps)+beta.  Cached."""
@@ -73,13 +101,22 @@ class VGG19(nn.Module):
             if step is None:
                 continue                                          # the pool was fused into the layer before it (or is the unused last one)
             pooled_next = i + 1 < len(plan) and plan[i + 1] is None
+            last = i + 2 >= len(plan)                             # layers[:40] ends on a pool whose output nothing reads
+            even = x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0
+            impl = self.conv_impl(dtype, nhwc, x.shape[1], step[0].shape[0], x.shape[0], x.shape[2], x.shape[3])
+            if impl != "library":                                 # bias + ReLU in the convolution's own store; the pool reads the map once
+                x = ops.conv3x3_bias_relu(x, step[0], step[1], impl)
+                if pooled_next:
+                    feats[scale] = x                              # captured BEFORE the pool (encoders.py:73-76)
+                    x = None if last else ops.maxpool2_nhwc(x) if even else F.max_pool2d(x, 2, 2)
+                    scale *= 2
+                continue
             x = F.conv2d(x, step[0], None, padding=1)
             if not pooled_next:
                 x = ops.bias_relu_(x, step[1])                    # one epilogue pass instead of add_ + relu_
                 continue
             feats[scale] = x                                      # captured BEFORE the pool (encoders.py:73-76)
-            last = i + 2 >= len(plan)                             # layers[:40] ends on a pool whose output nothing reads
-            if last or x.shape[-1] % 2 or x.shape[-2] % 2:
+            if last or not even:
                 ops.bias_relu_(x, step[1])
                 x = None if last else F.max_pool2d(x, 2, 2)
             else:

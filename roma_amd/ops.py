@@ -716,6 +716,53 @@ def bias_relu_pool2_(x, bias):
     return out
 
 
+def maxpool2_nhwc(x):
+    """MaxPool2d(2, 2) of a dense channels-last (B,C,H,W) map, H and W even: the map is read once and a quarter written.  For a
+    layer whose bias + ReLU the convolution already stored (conv3x3_bias_relu); bit-equal to bias_relu_pool2_'s pooled output on
+    the map that call leaves in place (encoders.py:68-78)."""
+    _need_gpu(x)
+    B, C, H, W = x.shape
+    assert _is_nhwc(x) and H % 2 == 0 and W % 2 == 0
+    out = torch.empty((B, H // 2, W // 2, C), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
+    check(_lib.load().roma_maxpool2_nhwc(_p(x), _p(out), B, C, H, W, _dt(x), _stream()), "roma_maxpool2_nhwc")
+    return out
+
+
+def conv3x3_instances():
+    """The CK type strings of the convolution instances conv3x3_bias_relu can run, in index order (no device needed)."""
+    import ctypes
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(256)
+    names = []
+    for i in range(lib.roma_conv3x3_bias_relu_instances(0, None, 0)):
+        check(min(0, lib.roma_conv3x3_bias_relu_instances(i, buf, len(buf))), "roma_conv3x3_bias_relu_instances")
+        names.append(buf.value.decode())
+    return names
+
+
+def conv3x3_bias_relu(x, w, bias, instance, out=None):
+    """relu(conv2d(x, w, padding=1) + bias) in one kernel — a VGG19-BN layer with BatchNorm folded (encoders.py:68-78): x (B,Cin,H,W)
+    and w (Cout,Cin,3,3) channels-last fp16, bias (Cout) fp16.  The accumulator is rounded to fp16 before the bias is added, as
+    F.conv2d followed by bias_relu_ does.  `instance` indexes conv3x3_instances().  `out` may be a channel slice of a wider
+    channels-last map (only its Cout channels are written)."""
+    _need_gpu(x, w, bias, out)
+    B, Cin, H, W = x.shape
+    Cout = w.shape[0]
+    assert w.shape == (Cout, Cin, 3, 3) and w.dtype == x.dtype == bias.dtype and bias.numel() == Cout and bias.is_contiguous()
+    assert w.permute(0, 2, 3, 1).is_contiguous(), "w must be channels-last (KYXC in memory)"
+    if out is None:
+        out = torch.empty((B, H, W, Cout), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
+    assert out.shape == (B, Cout, H, W) and out.dtype == x.dtype
+
+    def pitch(t):                                               # (B,C,H,W) view of pixel rows `pitch` elements apart
+        sb, sc, sh, sw = t.stride()
+        assert sc == 1 and sh == t.shape[3] * sw and sb == t.shape[2] * sh, "channels-last pixel rows expected"
+        return sw
+    check(_lib.load().roma_conv3x3_bias_relu(_p(x), _p(w), _p(bias), _p(out), B, Cin, Cout, H, W, _dt(x), pitch(x), pitch(out),
+                                             int(instance), _stream()), "roma_conv3x3_bias_relu")
+    return out
+
+
 def pointwise_mfma(rows, wt, bias, C, out=None):
     """rows (M, pitch) @ wt[:C,:C]^T + bias for 32 < C <= 160 on the matrix cores (matcher.py:102).  wt (kpad,kpad) [out][in] in
     rows' dtype, bias (kpad) fp32; out may be `rows` itself only for a full in-place update of the same rows."""
