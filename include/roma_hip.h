@@ -518,6 +518,41 @@ int roma_refine_absolute_pose(const double* X, const double* x, const double* K,
                               const unsigned char* mask_in, int P, int N, double threshold, int iters, double* R, double* t,
                               unsigned char* mask, double* cost, int* count, int* steps, void* stream);
 
+/* 3-D similarity registration from 3D-3D correspondences (csrc/similarity.hip): RANSAC with a 3-point minimal sample
+ * and the iterated closed-form refinement behind it — what puts two reconstructions, each in units of its own baseline, into one frame.
+ * Model Y ~ s R X + t: s > 0, R orthonormal with det +1; with_scale = 0 is the rigid model, s = 1.
+ * X, Y: (P,N,3) fp64, 8-byte aligned.  `threshold` is a distance in the units of Y: a correspondence is an inlier when
+ * |Y - (s R X + t)|^2 < threshold^2.  `scoring`: 0 = MSAC, 1 = MAGSAC++.  `iters` samples of 3 rows per pair, all drawn and scored, one
+ * model each (Umeyama's closed form, the rotation by Horn's quaternion); the draw is the hash of the RANSAC block above with stage 6
+ * and p = p0 + pair.  A row with a non-finite number is never sampled and never an inlier.  Both clouds are normalised per pair
+ * (X' = sX (X - cX), Y' = sY (Y - cY): centroids, mean distance sqrt 3; with_scale = 0: sX = sY), so the fp32 scoring depends neither on
+ * where the origins are nor on the ratio of the scales.  The library allocates nothing.
+ *
+ * roma_similarity_workspace: host function; the workspace size in bytes (<0 on bad arguments) and, if offsets != NULL, the byte offsets
+ *   of its 12 regions: [0]-[8] as roma_ransac_workspace with S = 3 and R = 1, where [0] is (cX, sX, cY, sY) per pair, [1] the scoring
+ *   records (P,N,4) fp32 = (X', Y'_x), NaN where a row is not usable, and [3] the rotations (P,iters,3,3) fp64; [9] (t', s')
+ *   (P,iters,4) fp64, the model of the normalised clouds: s = s' sX / sY, t = t' / sY + cY - s R cX; [10] (Y'_y, Y'_z) (P,N,2) fp32 of
+ *   the scoring records; [11] (P,N,6) fp64 = (X', Y'), the solver's copy.  The workspace must be 16-byte aligned.
+ * roma_similarity_hypotheses: normalisation, samples, the closed form and scoring into the workspace (all regions).
+ * roma_similarity_select: the lowest-cost slot per pair (lowest slot on ties), then lo_iters rounds of local optimisation: the closed
+ *   form on the inliers (weighted by W for MAGSAC++), kept only if the cost drops.  It reads the workspace roma_similarity_hypotheses
+ *   left (same P, N, iters, threshold, scoring), not X and Y again.  s: (P); R: (P,3,3); t: (P,3); mask: (P,N) uint8; valid: (P) int32.
+ *   A pair without a valid slot: s, R and t all zero, empty mask, valid = 0.
+ * roma_refine_similarity: from (s_in, R_in, t_in), at most `iters` rounds of the closed form on the matches with e < threshold^2, on the
+ *   sum over the usable matches (finite, allowed by mask_in — (P,N) uint8, NULL = all) of min(e, threshold^2) in fp64.  A round is kept
+ *   when cost' < cost (1 - 1e-12); the first that is not ends the loop.  A pair with fewer than 3 weighted matches, a configuration that
+ *   does not fix the rotation, an input that is not finite, or no round kept gets its input back bit for bit (steps = 0) with its own
+ *   mask, cost and count.  cost: (P) fp64 in squared Y units; count, steps: (P) int32.  One launch, no workspace. */
+long roma_similarity_workspace(int P, int N, int iters, long* offsets);
+int roma_similarity_hypotheses(const double* X, const double* Y, int P, int N, int iters, float threshold, int scoring, int with_scale,
+                               unsigned seed, int p0, void* ws, long ws_bytes, void* stream);
+int roma_similarity_select(const double* X, const double* Y, int P, int N, int iters, float threshold, int scoring, int with_scale,
+                           int lo_iters, const void* ws, long ws_bytes, double* s, double* R, double* t, unsigned char* mask, int* valid,
+                           void* stream);
+int roma_refine_similarity(const double* X, const double* Y, const double* s_in, const double* R_in, const double* t_in,
+                           const unsigned char* mask_in, int P, int N, double threshold, int iters, int with_scale, double* s, double* R,
+                           double* t, unsigned char* mask, double* cost, int* count, int* steps, void* stream);
+
 /* Two-view triangulation of matches under a known relative pose (csrc/triangulate.hip) — what a caller does with
  * the (R, t) of roma_recover_pose / roma_refine_pose: a point cloud of the sampled matches, or a depth map per image from every row of
  * the dense warp.  Convention of roma_recover_pose: x_B ~ K_B (R X_A + t).  Points are expressed in camera A's frame, in units of

@@ -50,6 +50,12 @@ from `triangulate` (camera A's frame, in baselines), from `depth_from_warp`, or 
 triangulate_nview.hip: fp32 per point, relative to the mean camera centre, from view constants prepared in fp64; a pairwise robust
 choice of the views, the point closest to their rays, Levenberg-Marquardt on the pixel error), and `depth_from_warps` runs it on the k
 warps of one image against k others, read in place: one depth map of that image from all of them.
+
+`find_similarity` and `refine_similarity` register two point clouds given row by row, Y ~ s R X + t (csrc/similarity.hip): 3-point
+RANSAC with Umeyama's closed form (the rotation by Horn's quaternion), scored by the distance in Y's units, and the closed form
+iterated on the truncated cost — what brings two reconstructions, each in units of its own baseline, into one frame.
+`register_depth_maps` does it for two depth maps of one image; `apply_similarity`, `transform_cameras` and `similarity_error` are the
+torch helpers around them.
 """
 from __future__ import annotations
 
@@ -1370,3 +1376,222 @@ def absolute_pose_hypotheses(X, x, K, threshold=2.0, max_iters=1000, seed=0, *, 
         "centroid": c,
         "scale": s,
     }
+
+
+# ------------------------------------------------------------------------------------------------------ similarity registration
+_SIM_REGIONS = 12
+
+
+def _clouds(X, Y):
+    """X, Y (N,3) or (P,N,3) fp32/fp64 device tensors of one shape -> contiguous (P,N,3) fp64 each, single-pair flag"""
+    if X.dim() not in (2, 3) or X.shape[-1] != 3 or Y.shape != X.shape:
+        raise ValueError(f"expected two clouds (N,3) or (P,N,3) of one shape, got {tuple(X.shape)} and {tuple(Y.shape)}")
+    for t in (X, Y):
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"points must be float32 or float64, got {t.dtype}")
+    single = X.dim() == 2
+    P, N = (1, X.shape[0]) if single else (X.shape[0], X.shape[1])
+    if N < 3:
+        raise ValueError(f"{N} correspondences, the minimal sample needs 3")
+    if P < 1:
+        raise ValueError("empty batch")
+    _need_gpu(X, Y)
+    return X.reshape(P, N, 3).to(torch.float64).contiguous(), Y.reshape(P, N, 3).to(torch.float64).contiguous(), single
+
+
+def similarity_workspace_layout(P, N, iters):
+    """(total bytes, [region offsets]) of the workspace of roma_similarity_hypotheses (include/roma_hip.h: 12 regions)"""
+    off = (ctypes.c_long * _SIM_REGIONS)()
+    total = _lib.load().roma_similarity_workspace(P, N, iters, ctypes.cast(off, ctypes.c_void_p))
+    if total < 0:
+        check(int(total), "roma_similarity_workspace")
+    return int(total), list(off)
+
+
+def _sim_chunks(P, N, iters):
+    """_chunks for the similarity workspace"""
+    per_pair, _ = similarity_workspace_layout(1, N, iters)
+    most = max(1, _WORKSPACE_LIMIT // per_pair)
+    n = -(-P // most)
+    step = -(-P // n)
+    return [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
+
+
+def _sim_hypotheses(Xc, Yc, threshold, iters, score, with_scale, seed, p0, ws):
+    check(_lib.load().roma_similarity_hypotheses(Xc.data_ptr(), Yc.data_ptr(), Xc.shape[0], Xc.shape[1], iters, float(threshold), score,
+                                                 int(bool(with_scale)), seed, p0, ws.data_ptr(), ws.numel(), _stream()),
+          "roma_similarity_hypotheses")
+
+
+def _refine_sim(s, R, t, Xw, Yw, threshold, iters, with_scale, m):
+    """roma_refine_similarity on prepared (P,...) tensors -> (s, R, t, mask bool), (cost, count, steps)"""
+    P, N = Xw.shape[0], Xw.shape[1]
+    dev = Xw.device
+    so = torch.empty((P,), dtype=torch.float64, device=dev)
+    Ro = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    to = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
+    cost = torch.empty((P,), dtype=torch.float64, device=dev)
+    count = torch.empty((P,), dtype=torch.int32, device=dev)
+    steps = torch.empty((P,), dtype=torch.int32, device=dev)
+    check(_lib.load().roma_refine_similarity(Xw.data_ptr(), Yw.data_ptr(), s.data_ptr(), R.data_ptr(), t.data_ptr(),
+                                             None if m is None else m.data_ptr(), P, N, float(threshold), int(iters),
+                                             int(bool(with_scale)), so.data_ptr(), Ro.data_ptr(), to.data_ptr(), out.data_ptr(),
+                                             cost.data_ptr(), count.data_ptr(), steps.data_ptr(), _stream()), "roma_refine_similarity")
+    return (so, Ro, to, out.bool()), (cost, count, steps)
+
+
+def find_similarity(X, Y, threshold, max_iters=1000, seed=None, lo_iters=3, refine_iters=0, *, with_scale=True, scoring="msac"):
+    """Similarity (s, R, t) with Y ~ s R X + t from putative 3D-3D correspondences with outliers, on the device (csrc/similarity.hip):
+    what puts two reconstructions — each known only up to the scale of its own baseline — into one frame, or a reconstruction onto a
+    ground-truth cloud.  X, Y: (N,3) or (P,N,3), fp32/fp64, row i of X corresponds to row i of Y.  RANSAC with max_iters samples of 3
+    rows per pair, all drawn and scored (Umeyama's closed form in fp64, the rotation by Horn's quaternion), the squared distance scored
+    in fp32 on clouds normalised per pair (so neither a far origin nor the ratio of the scales reaches fp32), lowest cost wins, then
+    lo_iters rounds of the closed form on the inliers.  threshold is a DISTANCE IN THE UNITS OF Y: row i is an inlier when
+    |Y_i - (s R X_i + t)| < threshold.  The noise of triangulated points grows with their depth (about quadratically, for a fixed
+    pixel noise), so for clouds from `triangulate` / `depth_from_warp` choose it for the far points you want kept, or gate the clouds by
+    parallax first.  with_scale=False estimates the rigid model (s = 1).  Rows with a NaN / inf in X or Y are never sampled and never
+    inliers (triangulate's invalid rows can be passed as NaN).  Returns (s fp64 () or (P,), R fp64 (3,3) or (P,3,3) orthonormal with
+    det +1, t fp64 (3,) or (P,3), mask bool); s, R and t all zero and an empty mask when no sample gives a model (collinear clouds,
+    fewer than 3 usable rows).  refine_iters > 0 polishes the RANSAC model by refine_similarity on all rows at the same threshold and
+    returns the refined model's mask.  scoring: "msac" or "magsac" (module docstring).  No host synchronisation."""
+    score = _scoring(scoring)
+    refine_iters = _refine_iters(refine_iters)
+    _args(threshold, max_iters, lo_iters)
+    Xw, Yw, single = _clouds(X, Y)
+    P, N = Xw.shape[0], Xw.shape[1]
+    iters, seed = int(max_iters), _seed(seed)
+    dev = Xw.device
+    s = torch.empty((P,), dtype=torch.float64, device=dev)
+    R = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    t = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((P, N), dtype=torch.uint8, device=dev)
+    valid = torch.empty((P,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    chunks = _sim_chunks(P, N, iters)
+    # one workspace, sized for the widest chunk, serves every chunk in stream order (a narrower chunk's layout is no larger)
+    total, _ = similarity_workspace_layout(max(b - a for a, b in chunks), N, iters)
+    ws = torch.empty((total,), dtype=torch.uint8, device=dev)
+    for a, b in chunks:
+        Xc, Yc = Xw[a:b], Yw[a:b]
+        _sim_hypotheses(Xc, Yc, threshold, iters, score, with_scale, seed, a, ws)
+        check(lib.roma_similarity_select(Xc.data_ptr(), Yc.data_ptr(), b - a, N, iters, float(threshold), score, int(bool(with_scale)),
+                                         int(lo_iters), ws.data_ptr(), total, s[a:b].data_ptr(), R[a:b].data_ptr(), t[a:b].data_ptr(),
+                                         mask[a:b].data_ptr(), valid[a:b].data_ptr(), _stream()), "roma_similarity_select")
+    if refine_iters > 0:
+        (s, R, t, mask), _ = _refine_sim(s, R, t, Xw, Yw, threshold, refine_iters, with_scale, None)
+    else:
+        mask = mask.bool()
+    return (s[0], R[0], t[0], mask[0]) if single else (s, R, t, mask)
+
+
+def refine_similarity(s, R, t, X, Y, threshold, iters=15, mask=None, return_info=False, *, with_scale=True):
+    """Refinement of a similarity (s, R, t) — of find_similarity — on the correspondences it was estimated from: at most `iters` rounds
+    of the closed-form weighted least-squares fit (Umeyama) on the rows within the threshold of the current model, on the sum over the
+    rows of min(e, threshold^2), e the squared distance |Y - (s R X + t)|^2 in Y units, in fp64.  Rows beyond the threshold or not
+    finite carry no weight, and `mask` (bool / uint8) optionally names the only rows that may carry any.  s () or (P,), R (3,3) or
+    (P,3,3), t (3,) or (P,3); X, Y as find_similarity.  Returns (s, R orthonormal, t, all fp64, mask bool: e < threshold^2 under the
+    returned model); with return_info also a dict of device tensors: cost (fp64, the truncated cost of the returned model), count (int32,
+    its inliers), steps (int32, the rounds kept).  A round is kept only if it lowers the cost, and the first that does not ends the
+    loop; a pair that cannot be refined (fewer than 3 weighted rows, rows that do not fix the rotation, a model that is not finite, no
+    round that lowers the cost) gets its model back bit for bit, with steps = 0.  with_scale=False keeps s = 1 in every round."""
+    _need_gpu(s, R, t)
+    _refine_args(threshold, iters)
+    Xw, Yw, single = _clouds(X, Y)
+    P, N = Xw.shape[0], Xw.shape[1]
+    if s.shape != (() if single else (P,)) or R.shape != ((3, 3) if single else (P, 3, 3)) or t.shape != ((3,) if single else (P, 3)):
+        raise ValueError(f"s {tuple(s.shape)}, R {tuple(R.shape)}, t {tuple(t.shape)} do not match the points {tuple(X.shape)}")
+    s0 = s.reshape(P).to(torch.float64).contiguous()
+    r0 = R.reshape(P, 3, 3).to(torch.float64).contiguous()
+    t0 = t.reshape(P, 3).to(torch.float64).contiguous()
+    m = _mask(mask, P, N, X)
+    res, info = _refine_sim(s0, r0, t0, Xw, Yw, threshold, iters, with_scale, m)
+    return _refined(res, info, single, return_info)
+
+
+def similarity_hypotheses(X, Y, threshold, max_iters=1000, seed=0, *, with_scale=True, scoring="msac"):
+    """Every hypothesis of one find_similarity call, before selection (batched (P,...) shapes even for a single pair): samples
+    (P,iters,3) int32 (a row of -1 for an invalid sample); s (P,iters), R (P,iters,3,3), t (P,iters,3) fp64 in the CALLER'S units (zero
+    where not valid); valid (P,iters) bool; cost (P,iters) fp64 of the chosen scoring in squared NORMALISED Y units, i.e. times
+    scale_Y^2 (+inf if invalid); count (P,iters) int32 inliers; centroid_X, centroid_Y (P,3), scale_X, scale_Y (P,) of the
+    normalisation.  Pair p draws what it draws in find_similarity with the same seed.  An inspection helper with score_hypotheses' batch
+    limit."""
+    score = _scoring(scoring)
+    _args(threshold, max_iters, 0)
+    Xw, Yw, _ = _clouds(X, Y)
+    P, N, iters = Xw.shape[0], Xw.shape[1], int(max_iters)
+    total, off = similarity_workspace_layout(P, N, iters)
+    if total > _WORKSPACE_LIMIT:
+        raise ValueError(f"similarity_hypotheses: {P} pairs need a {total >> 20} MiB workspace, over the {_WORKSPACE_LIMIT >> 20} MiB "
+                         "limit; call it on fewer pairs")
+    ws = torch.empty((total,), dtype=torch.uint8, device=Xw.device)
+    _sim_hypotheses(Xw, Yw, threshold, iters, score, with_scale, _seed(seed), 0, ws)
+    norm = _view(ws, off, 0, torch.float64, (P, 8))
+    cX, sX, cY, sY = norm[:, :3].clone(), norm[:, 3].clone(), norm[:, 4:7].clone(), norm[:, 7].clone()
+    R = _view(ws, off, 3, torch.float64, (P, iters, 3, 3)).clone()
+    ts = _view(ws, off, 9, torch.float64, (P, iters, 4))
+    valid = _view(ws, off, 4, torch.int32, (P, iters)) != 0
+    s = ts[..., 3] * (sX / sY)[:, None]
+    t = ts[..., :3] / sY[:, None, None] + cY[:, None, :] - s[..., None] * (R @ cX[:, None, :, None]).squeeze(-1)
+    return {
+        "samples": _view(ws, off, 2, torch.int32, (P, iters, 3)).clone(),
+        "s": torch.where(valid, s, torch.zeros_like(s)),
+        "R": R,
+        "t": torch.where(valid[..., None], t, torch.zeros_like(t)),
+        "valid": valid,
+        "cost": _view(ws, off, 7, torch.float64, (P, iters)).clone(),
+        "count": _view(ws, off, 8, torch.int32, (P, iters)).clone(),
+        "centroid_X": cX, "scale_X": sX, "centroid_Y": cY, "scale_Y": sY,
+    }
+
+
+def apply_similarity(X, s, R, t):
+    """s R X + t for points X (...,N,3) and a similarity s (...), R (...,3,3), t (...,3) of find_similarity: torch ops only, CPU or
+    device tensors."""
+    s, R, t = (torch.as_tensor(v, dtype=X.dtype, device=X.device) for v in (s, R, t))
+    return s[..., None, None] * (X @ R.transpose(-1, -2)) + t[..., None, :]
+
+
+def transform_cameras(R_cam, t_cam, s, R, t):
+    """Cameras x ~ K (R_cam X + t_cam) of the source frame, expressed in the destination frame Y = s R X + t of a similarity (of
+    find_similarity): R' = R_cam R^T, t' = s t_cam - R' t, so that K (R' Y + t') ~ K (R_cam X + t_cam) — the same pixels.  R_cam
+    (...,3,3), t_cam (...,3); s (), R (3,3), t (3,) or batched alike.  torch ops only, CPU or device tensors."""
+    s, R, t = (torch.as_tensor(v, dtype=R_cam.dtype, device=R_cam.device) for v in (s, R, t))
+    Rn = R_cam @ R.transpose(-1, -2)
+    return Rn, s[..., None] * t_cam - (Rn @ t[..., None]).squeeze(-1)
+
+
+def similarity_error(s, R, t, s_gt, R_gt, t_gt, at):
+    """Error of a similarity against (s_gt, R_gt, t_gt): (the geodesic angle of R^T R_gt in degrees, |log(s / s_gt)|, the distance
+    between the two images of the points `at` (...,N,3) divided by s_gt — in the units of the source cloud), batched, torch ops only,
+    CPU or device tensors."""
+    s_gt, R_gt, t_gt = (torch.as_tensor(v, dtype=R.dtype, device=R.device) for v in (s_gt, R_gt, t_gt))
+    cos = ((R * R_gt).sum((-1, -2)) - 1.0) / 2.0
+    e_R = torch.rad2deg(torch.acos(torch.clamp(cos, -1.0, 1.0)).abs())
+    e_s = torch.log(s / s_gt).abs()
+    d = torch.linalg.norm(apply_similarity(at, s, R, t) - apply_similarity(at, s_gt, R_gt, t_gt), dim=-1) / s_gt[..., None]
+    return e_R, e_s, d
+
+
+def register_depth_maps(depth_src, depth_dst, K, threshold, **kw):
+    """Similarity between two depth maps (H,W) of the SAME image, each in its own unit — e.g. of depth_from_warp against two partners:
+    the pixel grid (centres at +0.5, as lift_keypoints) is lifted with each map, X = depth_src K^-1 (u, v, 1) and Y likewise, cells where
+    either depth is <= 0 or not finite become NaN rows, and find_similarity(X, Y, threshold, **kw) registers them.  Returns (s, R, t,
+    mask (H,W)); s is the ratio of the units (R ~ I, t ~ 0 for maps of one image) — what gives the poses passed to depth_from_warps
+    their shared scale.  threshold in the units of depth_dst."""
+    _need_gpu(depth_src, depth_dst)
+    if depth_src.dim() != 2 or depth_src.shape != depth_dst.shape:
+        raise ValueError(f"expected two depth maps (H,W) of one shape, got {tuple(depth_src.shape)} and {tuple(depth_dst.shape)}")
+    H, W = depth_src.shape
+    dev = depth_src.device
+    Ki = _inverse_intrinsics(_intrinsics(K, 1, dev, "K"))[0]
+    v, u = torch.meshgrid(torch.arange(H, dtype=torch.float64, device=dev) + 0.5, torch.arange(W, dtype=torch.float64, device=dev) + 0.5,
+                          indexing="ij")
+    rays = (torch.stack([u, v, torch.ones_like(u)], -1) @ Ki.transpose(-1, -2)).reshape(H * W, 3)
+    ds, dd = depth_src.reshape(-1).to(torch.float64), depth_dst.reshape(-1).to(torch.float64)
+    ok = torch.isfinite(ds) & torch.isfinite(dd) & (ds > 0) & (dd > 0)
+    nan = torch.full_like(rays, float("nan"))
+    X = torch.where(ok[:, None], rays * ds[:, None], nan)
+    Y = torch.where(ok[:, None], rays * dd[:, None], nan)
+    s, R, t, mask = find_similarity(X, Y, threshold, **kw)
+    return s, R, t, mask.reshape(H, W)
