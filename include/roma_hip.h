@@ -615,6 +615,34 @@ int roma_triangulate_nview(const float* const* obs, const float* to_px, const un
                            float max_cos_parallax, float* points, float* depth, float* reproj, float* cos_parallax, unsigned* views,
                            unsigned char* valid, void* stream);
 
+/* Tracks from pairwise matches (csrc/tracks.hip): the sampled matches of M image pairs over V views (2 <= V <= 32),
+ * joined into tracks in the form roma_triangulate_nview reads.  tests/tracks_ref.py restates the definition; outputs are exact.
+ *   matches: (M,k,4) fp32 device, 16-byte aligned, normalised [xA, yA, xB, yB]; certainty: (M,k) fp32 device; mask: (M,k) uint8 device
+ *     or NULL; pairs: (M,2) int32 device, the views (a_m, b_m) of pair m; sizes: V x 2 ints in HOST memory, (H_v, W_v), 1 to 65536;
+ *   cell: 1 .. 64 pixels.  View v has ceil(H_v / cell) x ceil(W_v / cell) cells with global ids base_v + cy * Wc_v + cx, base the
+ *     running sum; their number C must be below 2^31.  M * k < 2^31; max_tracks >= 1, V * max_tracks < 2^30; 2 <= min_views <= V;
+ *     certainty_thresh finite, >= 0.
+ * An endpoint in view v is at px = (x + 1.0f) * (0.5f * W_v), py likewise, in cell ((int)floorf(px * inv), (int)floorf(py * inv)), inv
+ * = 1.0f / cell, and inside when 0 <= px < W_v, 0 <= py < H_v and the cell exists.  A match is usable when both endpoints are inside,
+ * its certainty is finite and > certainty_thresh, its mask is not 0, both views are in [0, V) and differ.  A cell with a usable
+ * endpoint is a node; its keypoint is the endpoint of the highest certainty, the lowest endpoint index (m * k + j) * 2 + side on a
+ * tie.  Usable matches are edges; a component's label is its lowest node id; it is conflicting with two nodes in one view and
+ * qualifies when it is not and sees at least min_views views.  Qualifying components get rows 0, 1, ... in ascending label order;
+ * rows >= max_tracks are dropped.
+ * Outputs, device, all required: x (V,max_tracks,2) fp32 pixels, NaN where a view does not see a track; visible (V,max_tracks) uint8;
+ * views (max_tracks) int32, bit v = view v sees the track; num_views (max_tracks) uint8; track_of_match (M,k) int32, the row of a
+ * usable match's track or -1; counts (4) int32: qualifying components before truncation, conflicting ones, ones below min_views, and a
+ * status word: 0, or 1 if an edge gave up after 2^20 rounds of the union's retry loop (never in correct operation).  Rows from
+ * min(counts[0], max_tracks) on stay empty.
+ * workspace: roma_tracks_workspace(V, sizes, cell, &cells) bytes (21 per cell and 12 per 256 cells), 16-byte aligned; the function
+ * returns a negative code for bad arguments and stores C in *cells (may be NULL).  Eight launches on `stream`, integer atomics only, no
+ * host synchronisation; nothing depends on the order in which threads arrive. */
+long roma_tracks_workspace(int V, const int* sizes, int cell, long* cells);
+int roma_build_tracks(const float* matches, const float* certainty, const unsigned char* mask, const int* pairs, const int* sizes, int M,
+                      int k, int V, int cell, float certainty_thresh, int min_views, int max_tracks, float* x, unsigned char* visible,
+                      int* views, unsigned char* num_views, int* track_of_match, int* counts, void* workspace, long workspace_size,
+                      void* stream);
+
 /* Ground-truth warp of key-points from two depth maps and a relative pose (csrc/depth_warp.hip): warp_kpts of the
  * reference (romatch/utils/utils.py:358-455; get_gt_warp is this on the pixel grid).  Convention: X_B = R X_A + t, T = [R | t].
  *   x: (P,N,·) fp32 device, 8-byte aligned, normalised key-points of image A in columns 0-1 of rows `x_stride` floats apart: 2 for

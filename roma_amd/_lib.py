@@ -106,6 +106,9 @@ SIGNATURES = {
     "roma_triangulate_nview": [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_long,
                                c_float, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p],
+    "roma_tracks_workspace": [c_int, c_void_p, c_int, c_void_p],
+    "roma_build_tracks": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
     "roma_warp_kpts": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                        ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p],
     "roma_dense_match_metrics": [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -126,7 +129,8 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
 }
 _RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long, "roma_essential_workspace": c_long,
-             "roma_race_select_workspace": c_long, "roma_absolute_pose_workspace": c_long, "roma_similarity_workspace": c_long}
+             "roma_race_select_workspace": c_long, "roma_absolute_pose_workspace": c_long, "roma_similarity_workspace": c_long,
+             "roma_tracks_workspace": c_long}
 
 _lib = None
 

@@ -56,6 +56,11 @@ RANSAC with Umeyama's closed form (the rotation by Horn's quaternion), scored by
 iterated on the truncated cost — what brings two reconstructions, each in units of its own baseline, into one frame.
 `register_depth_maps` does it for two depth maps of one image; `apply_similarity`, `transform_cameras` and `similarity_error` are the
 torch helpers around them.
+
+`build_tracks` joins the sampled matches of M image pairs over V views into multi-view tracks (csrc/tracks.hip): endpoints are
+quantised to cells of a few pixels, each cell is represented by its most certain endpoint, the matches are the edges of a lock-free
+union-find, and every component with at most one cell per view becomes a row of the `(V,T,2)` observations and `(V,T)` visibility
+that `triangulate_nview` takes — the step between `sample_batch` and structure, exact and independent of thread order.
 """
 from __future__ import annotations
 
@@ -959,6 +964,96 @@ def depth_from_warps(warps, certainties, R, t, K_A, K, H_A, W_A, sizes=None, *, 
     valid = valid.reshape(H, W)
     return MultiViewDepth(torch.where(valid, depth.reshape(H, W), 0.0), valid, _popcount(views).reshape(H, W), reproj.reshape(H, W),
                           points.reshape(H, W, 3))
+
+
+# ------------------------------------------------------------------------------------- tracks from pairwise matches
+_TRACKS_WORKSPACE_LIMIT = 2 << 30
+
+
+class Tracks:
+    """What build_tracks returns, device tensors: x (V,T,2) fp32 pixels, NaN where a view does not see a track; visible (V,T) bool;
+    views (T) int32, bit v set where view v sees the track, (views >> v) & 1; num_views (T) uint8; track_of_match (M,k) int32, the row
+    of the track a match belongs to or -1; counts (4) int32: qualifying components before truncation to T rows, conflicting
+    components, components below min_views, and a status word that is 0.  Rows from min(counts[0], T) on are empty."""
+    __slots__ = ("x", "visible", "views", "num_views", "track_of_match", "counts")
+
+    def __init__(self, x, visible, views, num_views, track_of_match, counts):
+        self.x, self.visible, self.views, self.num_views = x, visible, views, num_views
+        self.track_of_match, self.counts = track_of_match, counts
+
+    def __repr__(self):
+        return f"Tracks(x={tuple(self.x.shape)}, track_of_match={tuple(self.track_of_match.shape)}, device={self.x.device})"
+
+
+def build_tracks(matches, certainty, pairs, sizes, *, cell=4, certainty_thresh=0.0, mask=None, min_views=2, max_tracks):
+    """Multi-view tracks from the pairwise matches of M image pairs over V views (2 <= V <= 32), on the device (csrc/tracks.hip) — the
+    step between sample_batch and triangulate_nview.  A dense matcher has no repeatable keypoints, so every view is cut into cells of
+    `cell` pixels (1 to 64): a cell that receives a match endpoint is a node, represented by its endpoint of the highest certainty (the
+    first on a tie); a match is an edge between its two nodes; a connected component with at most one node per view and at least
+    min_views views is a track.  A component with two nodes in one view is conflicting and gives none.
+    matches: (M,k,4) normalised [xA, yA, xB, yB] as sample_batch returns them; certainty: (M,k); pairs: (M,2) integer tensor on the
+    device, the views (a_m, b_m) of pair m; sizes: V pairs (H_v, W_v) of Python ints; mask: optional (M,k) bool / uint8, for instance
+    the inlier masks of find_fundamental.  A match takes part when both endpoints lie inside their images, its certainty is finite
+    and > certainty_thresh (>= 0), its mask is set, and its two views are different views in [0, V).
+    Tracks are numbered by their lowest cell (view 0 first, row by row); max_tracks = T fixes the shape, rows beyond it are dropped
+    and counts[0] still has the full number.  Returns a Tracks; x and visible go to triangulate_nview(tracks.x, R, t, K,
+    visible=tracks.visible) as they are.  The result is a pure function of the inputs (integer atomics that commute, no float
+    atomics); tests/tracks_ref.py restates it exactly.  No host synchronisation: the call can be captured in a hipGraph."""
+    try:
+        sizes = [(int(h), int(w)) for h, w in sizes]
+    except (TypeError, ValueError):
+        raise ValueError("sizes: expected V pairs (H_v, W_v) of ints") from None
+    V = len(sizes)
+    if not 2 <= V <= _MAX_VIEWS:
+        raise ValueError(f"{V} views: 2 to {_MAX_VIEWS} are supported")
+    if any(not (1 <= h <= 65536 and 1 <= w <= 65536) for h, w in sizes):
+        raise ValueError(f"sizes: every (H_v, W_v) must be in [1, 65536], got {sizes}")
+    cell, min_views, T, thresh = int(cell), int(min_views), int(max_tracks), float(certainty_thresh)
+    if not 1 <= cell <= 64:
+        raise ValueError(f"cell must be in [1, 64] pixels, got {cell}")
+    if not 2 <= min_views <= V:
+        raise ValueError(f"min_views must be in [2, V={V}], got {min_views}")
+    if not (1 <= T and V * T < 1 << 30):
+        raise ValueError(f"max_tracks must be at least 1 with V * max_tracks < 2^30, got {T}")
+    if not 0.0 <= thresh < math.inf:
+        raise ValueError(f"certainty_thresh must be finite and not negative, got {certainty_thresh}")
+    lib = _lib.load()
+    size_tab = (ctypes.c_int * (2 * V))(*[s for hw in sizes for s in hw])
+    size_ptr = ctypes.cast(size_tab, ctypes.c_void_p)
+    ws_bytes = lib.roma_tracks_workspace(V, size_ptr, cell, None)
+    check(min(ws_bytes, 0), "roma_tracks_workspace")
+    if ws_bytes > _TRACKS_WORKSPACE_LIMIT:
+        raise ValueError(f"build_tracks: a workspace of {ws_bytes} bytes is above the limit of {_TRACKS_WORKSPACE_LIMIT}; use a larger cell "
+                         f"than {cell}")
+    if matches.dim() != 3 or matches.shape[-1] != 4 or not matches.is_floating_point():
+        raise ValueError(f"expected floating-point matches (M,k,4), got {tuple(matches.shape)} {matches.dtype}")
+    M, k = matches.shape[0], matches.shape[1]
+    if M < 1 or k < 1 or M * k >= 1 << 31:
+        raise ValueError(f"matches {tuple(matches.shape)}: M * k must be in [1, 2^31)")
+    if certainty.shape != (M, k) or not certainty.is_floating_point():
+        raise ValueError(f"certainty {tuple(certainty.shape)} {certainty.dtype} does not match the matches {tuple(matches.shape)}")
+    if pairs.shape != (M, 2) or pairs.is_floating_point() or pairs.dtype == torch.bool:
+        raise ValueError(f"pairs: expected an integer tensor ({M},2), got {tuple(pairs.shape)} {pairs.dtype}")
+    if mask is not None and mask.shape != (M, k):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the matches {tuple(matches.shape)}")
+    _need_gpu(matches, certainty, pairs, mask)
+    dev = matches.device
+    m = matches.to(torch.float32).contiguous()
+    c = certainty.to(torch.float32).contiguous()
+    pr = pairs.to(torch.int32).contiguous()
+    mk = None if mask is None else mask.to(torch.uint8).contiguous()
+    x = torch.empty((V, T, 2), dtype=torch.float32, device=dev)
+    visible = torch.empty((V, T), dtype=torch.bool, device=dev)
+    views = torch.empty((T,), dtype=torch.int32, device=dev)
+    num_views = torch.empty((T,), dtype=torch.uint8, device=dev)
+    track_of_match = torch.empty((M, k), dtype=torch.int32, device=dev)
+    counts = torch.empty((4,), dtype=torch.int32, device=dev)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    check(lib.roma_build_tracks(m.data_ptr(), c.data_ptr(), None if mk is None else mk.data_ptr(), pr.data_ptr(), size_ptr, M, k, V, cell,
+                                thresh, min_views, T, x.data_ptr(), visible.data_ptr(), views.data_ptr(), num_views.data_ptr(),
+                                track_of_match.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+          "roma_build_tracks")
+    return Tracks(x, visible, views, num_views, track_of_match, counts)
 
 
 # ------------------------------------------------------------------------------------- ground-truth warp from depth, dense metrics
