@@ -56,7 +56,14 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(TX* __restrict__ x, 
           float g[8];
           load8<float>(ls + e0, g);
 #pragma unroll
-          for (int i = 0; i < 8; ++i) v[c][i] = rnd<TX>(__builtin_fmaf(g[i], t[i], v[c][i]));
+          for (int i = 0; i < 8; ++i) {
+            // the sum is rounded to fp32, then to the stream dtype, like torch's own 16-bit addcmul.  Left to itself the compiler fuses
+            // two elements of an fp16 packet into v_fma_mixlo_f16 (ONE rounding) and not the other six: where the fp32 sum lands on the
+            // midpoint of two fp16 values (1 value in 2^13) those two came out 1 ulp away from what every other path stores
+            float s = __builtin_fmaf(g[i], t[i], v[c][i]);
+            if constexpr (sizeof(TX) == 2) asm("" : "+v"(s));
+            v[c][i] = rnd<TX>(s);
+          }
         } else {
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[c][i] = rnd<TX>(v[c][i] + t[i]);

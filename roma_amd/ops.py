@@ -914,6 +914,9 @@ def attention(qkv, n_valid=None, out=None):
     _need_gpu(qkv, out)
     B, N, three, H, d = qkv.shape
     assert three == 3 and qkv.is_contiguous()
+    nk = N if n_valid is None else int(n_valid)
+    if not 1 <= nk <= N:                                              # more keys than rows would read past the buffer
+        raise ValueError(f"attention: n_valid={nk} must be in 1..N={N}")
     if out is None:
         out = torch.empty((B, N, H * d), dtype=qkv.dtype, device=qkv.device)
     assert out.is_contiguous() and out.shape == (B, N, H * d) and out.dtype == qkv.dtype
