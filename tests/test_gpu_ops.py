@@ -9,6 +9,7 @@ import torch
 
 from tests import helpers as H
 from tests.golden import cases, recipes as R
+from tests.gp_ref import solve64                                   # fp64 reference solve on one host thread, shared with test_gp_stage.py
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -27,17 +28,6 @@ def _O():
 
 def maxerr(a, b):
     return float((a.detach().float().cpu() - b.detach().float().cpu()).abs().max())
-
-
-def solve64(K, F):
-    """fp64 reference solve on ONE host thread: multithreaded oneMKL getrf hangs on the GPU boxes' host CPUs (see
-    oracle._inv_single_thread)."""
-    nt = torch.get_num_threads()
-    torch.set_num_threads(1)
-    try:
-        return torch.linalg.solve(K.double(), F.double())
-    finally:
-        torch.set_num_threads(nt)
 
 
 def test_library_is_loaded_and_on_gpu():
