@@ -643,6 +643,45 @@ int roma_build_tracks(const float* matches, const float* certainty, const unsign
                       int* views, unsigned char* num_views, int* track_of_match, int* counts, void* workspace, long workspace_size,
                       void* stream);
 
+/* Bundle adjustment (csrc/bundle.hip): the V views (2 <= V <= 32) and N points (1 <= N <= 2^24) of ONE reconstruction
+ * refined together by Levenberg-Marquardt on the truncated reprojection cost, the cameras through the Schur complement of the points.
+ * Convention of roma_triangulate_nview: x_v ~ K_v (R_v X + t_v).  tests/bundle_ref.py restates the definition with the full normal
+ * equations.  A polish: it needs a start within a few pixels of the observations.
+ *   obs, to_px, visible: as roma_triangulate_nview with one row (rows = 1, row_len = N): point n of view v is the two fp32 at obs[v] +
+ *     n * point_stride (floats, even, >= 2; pointers 8-byte aligned), visible[v] (N) uint8 or NULL.  A (V,T,2) tensor of
+ *     roma_build_tracks is read in place with obs[v] = x + 2 T v, point_stride = 2;
+ *   K, R_in: (V,3,3) fp64 device; t_in: (V,3); X_in: (N,3) fp64 device, the points in the world frame; 16-byte aligned;
+ *   fixed: bit v = view v is held; at least one view and not all of them; threshold: pixels, positive; iters: 0 .. 50.
+ * Observation (v, n) is OBSERVED when its pixel is finite, visible[v][n] is not 0, view v is usable (K upper triangular with fx fy != 0,
+ * K, R, t finite) and X[n] is finite.  Under a state it is WEIGHTED when it is observed, its depth is positive and its squared pixel
+ * error e < threshold^2.  cost = sum over the observed of (weighted ? e : threshold^2).
+ * Parameters: 6 per free view, R' = exp([w]x) R, t' = exp([w]x) t + tau (the series of the other refinements, rows re-orthonormalised);
+ * 3 per point.  Held for a step: the fixed views, the views that are not usable, a free view without a weighted observation; a point
+ * with fewer than 2 weighted observations or whose damped 3 x 3 block has a pivot that is not positive.  A held point's weighted
+ * observations still enter the camera blocks, the point as a constant.  Gauss-Newton normal equations over the weighted observations,
+ * damped A + lambda diag A on the camera and the point blocks; lambda_0 = 1e-3, / 10 on a kept step (floor 1e-10), * 10 otherwise; a
+ * step is kept when cost' < cost (1 - 1e-12).  Everything is fp64 and relative to the mean of the centres of the usable views.
+ * Outputs, device, all required: R (V,3,3), t (V,3), X (N,3) fp64, 16-byte aligned; mask (V,N) uint8, the weighted observations under
+ * the returned state; cost (2) fp64, of the input and of the returned state; count (1) int32, the number of weighted observations;
+ * steps (1) int32, the steps kept; status (1) int32: 0, or bit 0 = a pivot of the reduced camera system was not positive, bit 1 = no
+ * usable free view, bit 2 = the cost of the input is not finite.  cost[1] <= cost[0] always.  With no step kept, or a status that is
+ * not 0, R, t, X are the input bit for bit, steps = 0, and cost[1], mask, count are the input's; a view or a point that was held at
+ * every kept step comes back bit for bit as well.
+ * workspace: roma_bundle_workspace(V, N, offsets) bytes, 16-byte aligned, need not be initialised; the function (host only) stores
+ * the byte offsets of its 11 regions in offsets (may be NULL) — the state record, the view constants, c0 and the camera step, the two
+ * pose buffers, the two point buffers, the moved flags, the reduced system, its per-block partials, the partial costs — each a
+ * multiple of 256, and returns a negative code for bad V or N.  With n = 6 V and M = n (n + 1) / 2 + 2 n + V the partials take
+ * 8 M min(ceil(N / 64), 256) bytes and the points 50 N.
+ * 5 + 6 iters launches on `stream`: per step accumulate, reduce, solve, propose, evaluate, decide.  The accept / reject decision is
+ * taken on the device; once the state record says finished, every later launch returns at once.  Sums are per-block partials added
+ * in block order: no floating-point atomics (count uses an integer one), bitwise reproducible.  No block waits for another, no host
+ * synchronisation: the call can be captured in a graph. */
+long roma_bundle_workspace(int V, int N, long* offsets);
+int roma_bundle_adjust(const float* const* obs, const float* to_px, const unsigned char* const* visible, long point_stride, const double* K,
+                       const double* R_in, const double* t_in, const double* X_in, int V, int N, unsigned fixed, double threshold, int iters,
+                       double* R, double* t, double* X, unsigned char* mask, double* cost, int* count, int* steps, int* status,
+                       void* workspace, long workspace_size, void* stream);
+
 /* Ground-truth warp of key-points from two depth maps and a relative pose (csrc/depth_warp.hip): warp_kpts of the
  * reference (romatch/utils/utils.py:358-455; get_gt_warp is this on the pixel grid).  Convention: X_B = R X_A + t, T = [R | t].
  *   x: (P,N,·) fp32 device, 8-byte aligned, normalised key-points of image A in columns 0-1 of rows `x_stride` floats apart: 2 for

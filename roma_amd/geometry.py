@@ -61,6 +61,12 @@ torch helpers around them.
 quantised to cells of a few pixels, each cell is represented by its most certain endpoint, the matches are the edges of a lock-free
 union-find, and every component with at most one cell per view becomes a row of the `(V,T,2)` observations and `(V,T)` visibility
 that `triangulate_nview` takes — the step between `sample_batch` and structure, exact and independent of thread order.
+
+`bundle_adjust` refines the cameras and the points of one reconstruction together (csrc/bundle.hip): Levenberg-Marquardt on the
+truncated reprojection cost in fp64, the points eliminated per point and the cameras solved through the reduced (Schur-complement)
+system, sums in a fixed order, the decision to keep a step taken on the device — the polish after `build_tracks`, the pose calls and
+`triangulate_nview`, which each fit one kind while holding the other.  `reconstruction_error` is its metric: the worst rotation and
+centre error and the median point error after a closed-form similarity alignment of the camera centres.
 """
 from __future__ import annotations
 
@@ -1690,3 +1696,138 @@ def register_depth_maps(depth_src, depth_dst, K, threshold, **kw):
     Y = torch.where(ok[:, None], rays * dd[:, None], nan)
     s, R, t, mask = find_similarity(X, Y, threshold, **kw)
     return s, R, t, mask.reshape(H, W)
+
+
+# ------------------------------------------------------------------------------------------------------------ bundle adjustment
+_BUNDLE_REGIONS = 11
+
+
+class BundleResult:
+    """What bundle_adjust returns, device tensors: R (V,3,3), t (V,3), points (N,3) fp64; mask (V,N) bool, the observations inside the
+    threshold (with positive depth) under the returned state; cost and cost0, fp64 scalars, the truncated cost of the result and of the
+    input (cost <= cost0); steps int32, the Levenberg-Marquardt steps kept (0: R, t, points are the input bit for bit); count int32,
+    the number of set mask entries; status int32 (include/roma_hip.h: 0, or why the input came back)."""
+    __slots__ = ("R", "t", "points", "mask", "cost", "cost0", "steps", "count", "status")
+
+    def __init__(self, R, t, points, mask, cost, cost0, steps, count, status=None):
+        self.R, self.t, self.points, self.mask, self.cost, self.cost0 = R, t, points, mask, cost, cost0
+        self.steps, self.count, self.status = steps, count, status
+
+    def __repr__(self):
+        return f"BundleResult(R={tuple(self.R.shape)}, points={tuple(self.points.shape)}, device={self.R.device})"
+
+
+def bundle_workspace_layout(V, N):
+    """-> (bytes, offsets of the 11 regions) of roma_bundle_workspace; raises ValueError on a bad shape"""
+    off = (ctypes.c_long * _BUNDLE_REGIONS)()
+    need = _lib.load().roma_bundle_workspace(int(V), int(N), ctypes.cast(off, ctypes.c_void_p))
+    if need < 0:
+        check(int(need), "roma_bundle_workspace")
+    return int(need), list(off)
+
+
+def _fixed_mask(fixed, V):
+    """a sequence of view indices or a (V,) bool tensor -> the 32-bit pattern of the held views"""
+    if torch.is_tensor(fixed) and fixed.dtype == torch.bool:
+        if fixed.shape != (V,):
+            raise ValueError(f"fixed: expected a ({V},) bool tensor, got {tuple(fixed.shape)}")
+        idx = [v for v, f in enumerate(fixed.tolist()) if f]
+    else:
+        idx = [int(v) for v in (fixed.tolist() if torch.is_tensor(fixed) else fixed)]
+    if any(not 0 <= v < V for v in idx):
+        raise ValueError(f"fixed: view indices must be in [0, {V}), got {idx}")
+    if not idx:
+        raise ValueError("fixed: at least one view must be held (the gauge)")
+    if len(set(idx)) == V:
+        raise ValueError("fixed: every view is held, nothing to refine")
+    bits = 0
+    for v in idx:
+        bits |= 1 << v
+    return bits
+
+
+def bundle_adjust(x, R, t, K, X, *, visible=None, threshold=2.0, iters=10, fixed=(0,), return_info=False):
+    """Cameras and points of one reconstruction refined TOGETHER (csrc/bundle.hip): Levenberg-Marquardt on the truncated reprojection
+    cost sum min(e, threshold^2) over the observations, the cameras solved through the Schur complement of the points — the step after
+    build_tracks -> estimate_pose / find_absolute_pose -> triangulate_nview, which each fit one kind while holding the other.
+    Convention of triangulate_nview: x_v ~ K_v (R_v X + t_v), 2 <= V <= 32 views, one reconstruction per call.
+    x: (V,N,2) pixels, any float dtype on the device, NaN where a view does not see a point, and visible (V,N) bool / uint8, optional —
+    `Tracks.x` and `Tracks.visible` of build_tracks as they come; R (V,3,3), t (V,3); K (3,3) shared or (V,3,3); X: (N,3) points, fp32
+    (`MultiViewTriangulation.points`) or fp64.  threshold in pixels; iters 0 to 50; fixed: the views that are held, a sequence of
+    indices or a (V,) bool tensor (a tensor on the device is read back: keep it on the host under graph capture).
+    This is a POLISH, as the other refine_* functions are: an observation more than `threshold` pixels off under the start counts as
+    an outlier, so the start has to reproject within a few pixels — a camera left with too few inliers does not move, and when no step
+    lowers the cost the input comes back bit for bit with steps = 0.  The gauge: with ONE fixed view the scale of the reconstruction is
+    left to the damping (it stays near the input's), TWO fixed views determine it.
+    A free view without an inlier and a point with fewer than two are held for that step; views and points held throughout come back
+    bit for bit.  Returns a BundleResult (R, t, points fp64, mask, cost, cost0, steps, count); with return_info=True also a dict with the
+    status word.  fp64 relative to the mean camera centre: the result does not depend on where the world's origin is.  Sums are taken
+    in a fixed order (no floating-point atomics): bitwise reproducible.  The decision to keep a step is taken on the device: no host
+    synchronisation, the call can be captured in a hipGraph."""
+    thr, iters = float(threshold), int(iters)
+    if not 0.0 < thr < 1e18:
+        raise ValueError(f"threshold must be positive pixels, got {threshold}")
+    if not 0 <= iters <= 50:
+        raise ValueError(f"iters must be in [0, 50], got {iters}")
+    _need_gpu(x, visible, X)
+    if x.dim() != 3 or x.shape[-1] != 2 or not x.is_floating_point():
+        raise ValueError(f"expected floating-point observations (V,N,2), got {tuple(x.shape)} {x.dtype}")
+    V, N = x.shape[0], x.shape[1]
+    if not 2 <= V <= _MAX_VIEWS:
+        raise ValueError(f"{V} views: 2 to {_MAX_VIEWS} are supported")
+    if N < 1:
+        raise ValueError("no points")
+    if X.shape != (N, 3) or not X.is_floating_point():
+        raise ValueError(f"points {tuple(X.shape)} {X.dtype}: expected floating-point ({N},3)")
+    if visible is not None and visible.shape != (V, N):
+        raise ValueError(f"visible {tuple(visible.shape)} does not match the observations {tuple(x.shape)}")
+    bits = _fixed_mask(fixed, V)
+    dev = x.device
+    xs = x.to(torch.float32).contiguous()
+    vis = None if visible is None else visible.to(torch.uint8).contiguous()
+    Rp, tp = _poses(R, t, V, dev)
+    Kp = _intrinsics(K, V, dev, "K")
+    Xp = X.to(torch.float64).contiguous()
+    need, _ = bundle_workspace_layout(V, N)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    Ro, to, Xo, cost = torch.empty((V, 3, 3), **f64), torch.empty((V, 3), **f64), torch.empty((N, 3), **f64), torch.empty((2,), **f64)
+    mask = torch.empty((V, N), dtype=torch.uint8, device=dev)
+    ints = torch.empty((3,), dtype=torch.int32, device=dev)                       # count, steps, status
+    obs_tab = (ctypes.c_void_p * V)(*[xs.data_ptr() + 8 * N * v for v in range(V)])
+    vis_tab = None if vis is None else (ctypes.c_void_p * V)(*[vis.data_ptr() + N * v for v in range(V)])
+    check(_lib.load().roma_bundle_adjust(ctypes.cast(obs_tab, ctypes.c_void_p), None, None if vis_tab is None else ctypes.cast(vis_tab, ctypes.c_void_p),
+                                         2, Kp.data_ptr(), Rp.data_ptr(), tp.data_ptr(), Xp.data_ptr(), V, N, bits, thr, iters, Ro.data_ptr(),
+                                         to.data_ptr(), Xo.data_ptr(), mask.data_ptr(), cost.data_ptr(), ints.data_ptr(), ints.data_ptr() + 4,
+                                         ints.data_ptr() + 8, ws.data_ptr(), need, _stream()),
+          "roma_bundle_adjust")
+    res = BundleResult(Ro, to, Xo, mask.bool(), cost[1], cost[0], ints[1], ints[0], ints[2])
+    return (res, {"status": ints[2]}) if return_info else res
+
+
+def reconstruction_error(R, t, X, R_gt, t_gt, X_gt):
+    """A reconstruction (R (V,3,3), t (V,3), X (N,3)) against the truth, whatever frame and unit it is in: the camera centres C_v =
+    -R_v^T t_v are aligned to the true ones by the closed-form similarity (Umeyama: C_gt ~ s Q C + tau, what similarity.hip's
+    refinement computes), then -> (the worst rotation error of a view in degrees, the worst distance of an aligned centre from the true
+    one, the median distance of an aligned point from the true one; rows of X or X_gt that are not finite are left out), fp64 scalars.
+    torch ops only, CPU or device tensors (the 3 x 3 SVD runs on the host).  Three views or more whose centres are not collinear
+    determine the alignment; with fewer the rotation about the baseline is free and the figures mean little."""
+    R, t, X, R_gt, t_gt, X_gt = (torch.as_tensor(v).to(torch.float64) for v in (R, t, X, R_gt, t_gt, X_gt))
+    dev = R.device
+    R_gt, t_gt, X_gt = R_gt.to(dev), t_gt.to(dev), X_gt.to(dev)
+    C = -(R.transpose(-1, -2) @ t[..., None]).squeeze(-1)
+    Cg = -(R_gt.transpose(-1, -2) @ t_gt[..., None]).squeeze(-1)
+    mc, mg = C.mean(0), Cg.mean(0)
+    A, B = C - mc, Cg - mg
+    U, S, Vh = torch.linalg.svd((B.T @ A).cpu())
+    d = torch.ones(3, dtype=torch.float64)
+    d[2] = torch.sign(torch.linalg.det(U @ Vh))
+    Q = (U @ torch.diag(d) @ Vh).to(dev)
+    s = (S * d).sum().to(dev) / (A * A).sum()
+    tau = mg - s * (Q @ mc)
+    cos = (((R @ Q.T) * R_gt).sum((-1, -2)) - 1.0) / 2.0
+    e_R = torch.rad2deg(torch.acos(torch.clamp(cos, -1.0, 1.0))).max()
+    e_C = torch.linalg.norm(s * (C @ Q.T) + tau - Cg, dim=-1).max()
+    dX = torch.linalg.norm(s * (X @ Q.T) + tau - X_gt, dim=-1)
+    e_X = dX[torch.isfinite(dX)].median()
+    return e_R, e_C, e_X
