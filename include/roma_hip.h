@@ -682,6 +682,40 @@ int roma_bundle_adjust(const float* const* obs, const float* to_px, const unsign
                        double* R, double* t, double* X, unsigned char* mask, double* cost, int* count, int* steps, int* status,
                        void* workspace, long workspace_size, void* stream);
 
+/* Multi-view depth-map fusion (csrc/depth_fuse.hip): the depth maps of V posed views (2 <= V <= 32) checked against
+ * one another by forward-backward reprojection, one owner chosen per surface point, and the owners compacted into one cloud.
+ * Convention of roma_triangulate_nview: x_v ~ K_v (R_v X + t_v); pixel (row i, column j) of a map is at (u, v) = (j + 0.5, i + 0.5) in
+ * the pixels K_v refers to (the caller folds a map-to-image scale into K_v).  tests/fuse_depth_ref.py restates the definition.
+ *   depths: HOST table of V device pointers, map v is (H_v, W_v) fp32 contiguous, 4-byte aligned, read in place; a depth that is not a
+ *     finite positive number is a hole;  dims: HOST table of 2 V ints, H_v, W_v (1 to 32768 each; all maps together at most 2^31 - 1
+ *     pixels);  K, R: (V,3,3), t: (V,3) fp64 device.  A view is usable when K_v is upper triangular with fx fy k22 != 0 and K_v, R_v,
+ *     t_v are finite; an unusable view sees nothing and is seen by nothing.
+ *   max_reproj_error (pixels of the reference map) and max_depth_error (relative) positive; 2 <= min_views <= V; max_points >= 1.
+ * Pass 1, per pixel (r, i, j) with a depth d, every usable s != r in ascending order: X = R_r^T (K_r^-1 (u d, v d, d) - t_r), q = K_s
+ * (R_s X + t_s), skip s unless q.z > 0; (u_s, v_s) = q.xy / q.z; d_s = the bilinear sample of map s there (taps floor(u_s - 0.5) and
+ * the next, likewise v), skip s unless all four taps are inside the map and none is a hole; p = the projection into r of (u_s, v_s,
+ * d_s) lifted from s, skip s unless p.z > 0; s is consistent when |p.xy / p.z - (u, v)| < max_reproj_error and |p.z - d| / d <
+ * max_depth_error.  The kernel evaluates q = d M_rs (u, v, 1) + e_rs with M_rs = K_s R_s R_r^T K_r^-1 and e_rs = K_s (t_s - R_s R_r^T
+ * t_r) prepared once per pair, everything in fp64: the world's origin cancels in e_rs.
+ * Pass 2: a valid pixel is a duplicate when for some s < r with bit s in its views the pixel (floor v_s, floor u_s) of s is valid and
+ * has bit r in its views.  Pass 3: the valid pixels that are not duplicates, in the order (view, row, column), fill the cloud.
+ * Outputs, device, all required.  Per pixel, flat over the views (view v starts at the sum of the pixel counts before it): depth fp32,
+ * the mean of d and the consistent p.z added in view order, 0 where not valid; valid uint8, num_views >= min_views; views int32, bit r
+ * and the consistent views' bits (0 for a hole or an unusable view); num_views uint8, its popcount.  The cloud, max_points rows:
+ * points (·,3) fp32 = R_r^T (K_r^-1 (u, v, 1) depth - t_r) in fp64 from the fused fp32 depth; view uint8; pixel int32 = i W_r + j;
+ * point_views int32; rows from min(counts[0], max_points) on are 0 with pixel = -1.  counts (4) int32: pixels emitted before
+ * truncation, valid pixels, duplicates, and a status word that is 0.
+ * workspace: roma_depth_fuse_workspace(V, total_pixels, out_bytes) bytes, 16-byte aligned, need not be initialised: one flag per pixel
+ * and 12 bytes per block of 1024 pixels (at most total_pixels / 1024 + V blocks), each rounded up to 256; the function (host only)
+ * stores the two sizes in out_bytes (may be NULL) and returns a negative code for bad V or total_pixels.
+ * Five launches on `stream`: consistency, ownership, the scan of the per-block counts by one workgroup, clear, cloud.  No atomics, no
+ * block waits for another, no host synchronisation: bitwise reproducible, and the call can be captured in a graph. */
+long roma_depth_fuse_workspace(int V, long total_pixels, long* out_bytes);
+int roma_depth_fuse(const float* const* depths, const int* dims, const double* K, const double* R, const double* t, int V,
+                    double max_reproj_error, double max_depth_error, int min_views, int max_points, float* depth, unsigned char* valid,
+                    int* views, unsigned char* num_views, float* points, unsigned char* view, int* pixel, int* point_views, int* counts,
+                    void* workspace, long workspace_size, void* stream);
+
 /* Ground-truth warp of key-points from two depth maps and a relative pose (csrc/depth_warp.hip): warp_kpts of the
  * reference (romatch/utils/utils.py:358-455; get_gt_warp is this on the pixel grid).  Convention: X_B = R X_A + t, T = [R | t].
  *   x: (P,N,·) fp32 device, 8-byte aligned, normalised key-points of image A in columns 0-1 of rows `x_stride` floats apart: 2 for

@@ -67,6 +67,11 @@ truncated reprojection cost in fp64, the points eliminated per point and the cam
 system, sums in a fixed order, the decision to keep a step taken on the device — the polish after `build_tracks`, the pose calls and
 `triangulate_nview`, which each fit one kind while holding the other.  `reconstruction_error` is its metric: the worst rotation and
 centre error and the median point error after a closed-form similarity alignment of the camera centres.
+
+`fuse_depth_maps` is the dense counterpart (csrc/depth_fuse.hip): the depth maps of V posed views — `depth_from_warps` once per image —
+are checked against one another by forward-backward reprojection in fp64, every pixel keeps the views that agree with it and the mean
+of their depths, each surface point is owned by the lowest view that sees it, and the owners are compacted in a fixed order into one
+cloud of a fixed shape.
 """
 from __future__ import annotations
 
@@ -1803,6 +1808,146 @@ def bundle_adjust(x, R, t, K, X, *, visible=None, threshold=2.0, iters=10, fixed
           "roma_bundle_adjust")
     res = BundleResult(Ro, to, Xo, mask.bool(), cost[1], cost[0], ints[1], ints[0], ints[2])
     return (res, {"status": ints[2]}) if return_info else res
+
+
+# ------------------------------------------------------------------------------------------------------------ depth-map fusion
+class FusedDepth:
+    """What fuse_depth_maps returns, device tensors.  Per view and pixel — lists of (H_v, W_v) tensors when the maps came as a list, (V,H,W)
+    tensors when they came stacked: depth fp32, the mean of the pixel's own depth and the depths the consistent views give it, 0 where
+    not valid; valid bool; views int32, the bit pattern of the pixel's own view and the consistent ones, (views >> v) & 1; num_views
+    uint8.  The cloud, T = max_points rows: points (T,3) fp32 in the frame of the poses; view (T) uint8 and pixel (T) int32 = row * W_v +
+    column, where a point comes from; point_views (T) int32; rows from min(counts[0], T) on are 0 with pixel = -1.  counts (4) int32:
+    pixels emitted before truncation to T rows, valid pixels, duplicates, and a status word that is 0."""
+    __slots__ = ("depth", "valid", "views", "num_views", "points", "view", "pixel", "point_views", "counts")
+
+    def __init__(self, depth, valid, views, num_views, points, view, pixel, point_views, counts):
+        self.depth, self.valid, self.views, self.num_views = depth, valid, views, num_views
+        self.points, self.view, self.pixel, self.point_views, self.counts = points, view, pixel, point_views, counts
+
+    def __repr__(self):
+        return f"FusedDepth(views={len(self.depth)}, points={tuple(self.points.shape)}, device={self.points.device})"
+
+
+def depth_fuse_workspace(V, total_pixels):
+    """-> bytes of roma_depth_fuse_workspace; raises ValueError on a bad shape"""
+    need = _lib.load().roma_depth_fuse_workspace(int(V), int(total_pixels), None)
+    if need < 0:
+        check(int(need), "roma_depth_fuse_workspace")
+    return int(need)
+
+
+def fuse_depth_maps(depths, R, t, K, *, sizes=None, max_reproj_error=1.0, max_depth_error=0.01, min_views=2, max_points):
+    """The depth maps of V posed views (2 <= V <= 32) checked against one another and merged into ONE cloud (csrc/depth_fuse.hip) — the
+    geometric consistency filter and fusion that multi-view stereo runs after its depth maps, and the step after depth_from_warps,
+    which gives every image a map of its own.  Convention of find_absolute_pose / triangulate_nview: x_v ~ K_v (R_v X + t_v); pixel (row
+    i, column j) of a map is at (j + 0.5, i + 0.5), as in lift_keypoints.
+    depths: a list or tuple of V maps (H_v, W_v), shapes free per view, or one (V,H,W) tensor: contiguous fp32 on the device, read in
+    place; anything else is refused (make it .float().contiguous()).  A depth that is 0, negative or not finite is a hole.  R (V,3,3), t
+    (V,3); K (3,3) shared or (V,3,3); sizes: V pairs (H_img, W_img), the image size K_v refers to, default the map's own shape — K_v is
+    scaled by diag(W_v / W_img, H_v / H_img, 1), so a depth_from_warps map at match resolution goes in with the K_A that made it.  A
+    view whose K is singular or not upper triangular, or whose pose is not finite, sees nothing and is seen by nothing.
+    Consistency: a pixel of view r with depth d is lifted and projected into every other usable view s (ascending; in front of s only);
+    the depth of s is sampled bilinearly there, only where all four taps are inside the map and none is a hole; that sample is lifted
+    from s and projected back into r; s is consistent when it comes back in front of r within max_reproj_error pixels (of map r) of
+    where it started and its depth p.z has |p.z - d| / d < max_depth_error.  views = the pixel's own bit and the consistent views',
+    valid = num_views >= min_views (2 <= min_views <= V), depth = the mean of d and the consistent p.z.
+    Ownership: a valid pixel is a duplicate when a consistent view s < r has, at the pixel the projection falls into, a valid pixel that
+    counts r as consistent.  Pixels of the lowest view are never duplicates and every duplicate points to a lower view, so every surface
+    point is emitted at least once.
+    Cloud: the valid pixels that are not duplicates, in the order (view, row, column); max_points = T fixes the shape, rows beyond it are
+    dropped and counts[0] still has the full number.  Returns a FusedDepth.  fp64 per pixel from the fp32 depths, on pair constants in
+    which the world's origin has cancelled; no atomics, so two calls agree bit for bit; tests/fuse_depth_ref.py restates it exactly.  No
+    host synchronisation: the call can be captured in a hipGraph."""
+    reproj, rel, min_views = float(max_reproj_error), float(max_depth_error), int(min_views)
+    if not 0.0 < reproj < math.inf:
+        raise ValueError(f"max_reproj_error must be positive finite pixels, got {max_reproj_error}")
+    if not 0.0 < rel < math.inf:
+        raise ValueError(f"max_depth_error must be positive and finite, got {max_depth_error}")
+    try:
+        T = int(max_points)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_points: expected an int, got {max_points!r}") from None
+    if not 1 <= T < 1 << 31:
+        raise ValueError(f"max_points must be in [1, 2^31), got {max_points}")
+    stacked = torch.is_tensor(depths)
+    if stacked:
+        if depths.dim() != 3:
+            raise ValueError(f"depths: expected a list or tuple of (H,W) maps or one (V,H,W) tensor, got {tuple(depths.shape)}")
+        maps = [depths[v] for v in range(depths.shape[0])]
+    elif isinstance(depths, (list, tuple)) and all(torch.is_tensor(d) for d in depths):
+        maps = list(depths)
+    else:
+        raise ValueError("depths: expected a list or tuple of (H,W) tensors, or one (V,H,W) tensor")
+    V = len(maps)
+    if not 2 <= V <= _MAX_VIEWS:
+        raise ValueError(f"{V} views: 2 to {_MAX_VIEWS} are supported")
+    if not 2 <= min_views <= V:
+        raise ValueError(f"min_views must be in [2, V={V}], got {min_views}")
+    for i, d in enumerate(maps):
+        if d.dim() != 2 or not (1 <= d.shape[0] <= 32768 and 1 <= d.shape[1] <= 32768):
+            raise ValueError(f"depth map {i}: expected (H,W) with sides in [1, 32768], got {tuple(d.shape)}")
+    dims = [(int(d.shape[0]), int(d.shape[1])) for d in maps]
+    total = sum(h * w for h, w in dims)
+    if total >= 1 << 31:
+        raise ValueError(f"the maps have {total} pixels in all, at most 2^31 - 1 are supported")
+    if sizes is None:
+        scale = [(1.0, 1.0)] * V
+    else:
+        try:
+            sizes = [(int(h), int(w)) for h, w in sizes]
+        except (TypeError, ValueError):
+            raise ValueError("sizes: expected V pairs (H_img, W_img) of ints") from None
+        if len(sizes) != V or any(h < 1 or w < 1 for h, w in sizes):
+            raise ValueError(f"sizes: expected {V} pairs (H_img, W_img) of positive ints, got {sizes}")
+        scale = [(w / wi, h / hi) for (h, w), (hi, wi) in zip(dims, sizes)]
+    for name, v, shapes in (("R", R, ((V, 3, 3),)), ("t", t, ((V, 3),)), ("K", K, ((3, 3), (V, 3, 3)))):
+        if tuple(getattr(v, "shape", ())) not in shapes:
+            raise ValueError(f"{name}: expected {' or '.join(str(s) for s in shapes)}, got {tuple(getattr(v, 'shape', ()))}")
+    _need_gpu(*maps)
+    dev = maps[0].device
+    for i, d in enumerate(maps):
+        if d.dtype != torch.float32 or not d.is_contiguous() or d.data_ptr() % 4:
+            raise ValueError(f"depth map {i}: {d.dtype} with strides {d.stride()} cannot be read in place (contiguous float32); pass "
+                             ".float().contiguous() maps")
+    Rp, tp = _poses(R, t, V, dev)
+    Kp = _intrinsics(K, V, dev, "K")
+    if any(sc != (1.0, 1.0) for sc in scale):
+        Kp = Kp.clone()                                       # _intrinsics may have handed back the caller's own tensor
+    for v, (sx, sy) in enumerate(scale):                      # Python scalars: kernel arguments, no copy from the host
+        if sx != 1.0:
+            Kp[v, 0] *= sx
+        if sy != 1.0:
+            Kp[v, 1] *= sy
+    need = depth_fuse_workspace(V, total)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    depth = torch.empty((total,), dtype=torch.float32, device=dev)
+    valid = torch.empty((total,), dtype=torch.bool, device=dev)
+    views = torch.empty((total,), dtype=torch.int32, device=dev)
+    num_views = torch.empty((total,), dtype=torch.uint8, device=dev)
+    points = torch.empty((T, 3), dtype=torch.float32, device=dev)
+    view = torch.empty((T,), dtype=torch.uint8, device=dev)
+    pixel = torch.empty((T,), dtype=torch.int32, device=dev)
+    point_views = torch.empty((T,), dtype=torch.int32, device=dev)
+    counts = torch.empty((4,), dtype=torch.int32, device=dev)
+    ptr_tab = (ctypes.c_void_p * V)(*[d.data_ptr() for d in maps])
+    dim_tab = (ctypes.c_int * (2 * V))(*[s for hw in dims for s in hw])
+    check(_lib.load().roma_depth_fuse(ctypes.cast(ptr_tab, ctypes.c_void_p), ctypes.cast(dim_tab, ctypes.c_void_p), Kp.data_ptr(), Rp.data_ptr(),
+                                      tp.data_ptr(), V, reproj, rel, min_views, T, depth.data_ptr(), valid.data_ptr(), views.data_ptr(),
+                                      num_views.data_ptr(), points.data_ptr(), view.data_ptr(), pixel.data_ptr(), point_views.data_ptr(),
+                                      counts.data_ptr(), ws.data_ptr(), need, _stream()),
+          "roma_depth_fuse")
+    del maps                                                  # alive until the launches are queued; the stream orders the rest
+
+    def per_view(flat):
+        if stacked:
+            return flat.view(V, *dims[0])
+        out, at = [], 0
+        for h, w in dims:
+            out.append(flat[at:at + h * w].view(h, w))
+            at += h * w
+        return out
+
+    return FusedDepth(per_view(depth), per_view(valid), per_view(views), per_view(num_views), points, view, pixel, point_views, counts)
 
 
 def reconstruction_error(R, t, X, R_gt, t_gt, X_gt):
