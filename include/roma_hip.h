@@ -682,6 +682,75 @@ int roma_bundle_adjust(const float* const* obs, const float* to_px, const unsign
                        double* R, double* t, double* X, unsigned char* mask, double* cost, int* count, int* steps, int* status,
                        void* workspace, long workspace_size, void* stream);
 
+/* Motion averaging (csrc/motion_average.hip): the V cameras of ONE reconstruction from the pairwise poses of its pose
+ * graph and its tracks — the start that roma_bundle_adjust polishes.  Two stages, fp64.  A view is x_v ~ K_v (R_v X + t_v)
+ * (roma_triangulate_nview); edge m, pairs[m] = (a, b), carries X_b = R_rel X_a + t_rel (roma_recover_pose).  tests/motion_ref.py
+ * restates both.
+ *
+ * roma_rotation_average: the rotations, 2 <= V <= 32 views, 1 <= M <= 4096 edges.
+ *   R_rel: (M,3,3) fp64 device, 16-byte aligned; pairs: (M,2) int32; weights: (M) fp64 or NULL (all 1); root: the view whose
+ *   rotation is the identity; sigma_deg > 0; iters: 0 .. 50.
+ * Edge m is USABLE when a != b, both are in [0, V), R_rel[m] is finite and its weight is finite and positive.  Start: the maximum-
+ * weight spanning tree grown from the root — repeatedly the usable edge with exactly one end in the tree and the largest weight, the
+ * lowest index on a tie, gives R_b = R_rel R_a or R_a = R_rel^T R_b; R_root = I.  A view that is never reached comes back as NaN with
+ * valid = 0.  Then `iters` rounds over the usable edges between reached views:
+ *   r_m = log(R_b^T R_rel,m R_a): w = vee(D - D^T) / 2, theta = atan2(|w|, (tr D - 1) / 2), r = w theta / |w| (r = w where |w| < 1e-12);
+ *   omega_m = weight_m / max(|r_m|, 1e-3) in the rounds below iters / 2 (integer division: the L1 phase), afterwards
+ *     weight_m (s^2 / (s^2 + |r_m|^2))^2 with s = sigma_deg in radians;
+ *   the weighted graph Laplacian over the reached views without the root, L[b][b] += omega, L[a][a] += omega, L[a][b] -= omega,
+ *     L[b][a] -= omega, rhs[b] += omega r, rhs[a] -= omega r (the rows and columns of the root are left out), solved by Cholesky for
+ *     delta (a pivot must be positive and finite);
+ *   R_v <- R_v exp([delta_v]x): the series of the other refinements (a delta longer than 1 rad is scaled to 1), rows re-orthonormalised.
+ * Outputs, device, all required: R (V,3,3) fp64, 16-byte aligned; valid (V) uint8; residual (M) fp64, |r_m| under the returned state,
+ * NaN for an edge that is not usable or not reached (it is the kernel's scratch while it runs); status (1) int32: 0, or bit 0 = a pivot
+ * was not positive, and the start comes back.
+ * ONE launch of one workgroup of 128 threads (a view x 4 slices of the edges; a Laplacian entry is the sum of its four slices, each in
+ * edge order), no workspace, no atomics, no host synchronisation.
+ *
+ * roma_global_positions: the camera centres and the points under those rotations — the linear known-rotation problem, 3 <= V <= 32
+ * views, 1 <= N <= 2^24 points, 1 <= M <= 4096 edges.
+ *   obs, to_px, visible, point_stride: the observation table of roma_bundle_adjust, read the same way;
+ *   K, R: (V,3,3) fp64 device (R: the output of roma_rotation_average); pairs: (M,2) int32; t_rel: (M,3) fp64, only its direction is
+ *   used; root: the view at the origin; threshold: pixels, positive; rounds: 2 .. 8.
+ * View v is usable when K_v is upper triangular with fx fy != 0 and K_v, R_v are finite; an observation is SEEN when its pixel is finite,
+ * visible[v][n] is not 0 and the view is usable.  Bearing d = R_v^T h / |h| with h = K_v^-1 (x, y, 1); a_v = threshold / sqrt(|fx fy|);
+ * P = I - d d^T.  Edge m is usable when a != b are usable views and t_rel[m] is finite and not 0; b_m = -R_b^T t_rel,m / |t_rel,m|.
+ * Round-0 weights, a majority vote: for a seen (v, n), every usable edge m that joins v to a view u that also sees n counts (cnt += 1,
+ * duplicates too) and agrees (vote += 1) when |(d_vn x d_un) . b_m| < 2 max(a_v, a_u), the cross product left as it is; w = 1 when
+ * vote >= 1 and 2 vote >= cnt, else 0.
+ * Round r = 0 .. rounds - 1:
+ *   A_n = sum_v w P; point n is SOLVED when it was solved in every earlier round, at least two of its weights are positive and
+ *     det A_n > 1e-12 (tr A_n)^3; otherwise its weights are 0 from then on;
+ *   over the solved points S (3 V x 3 V) gets S_vv += w P and, for all v, u, S_vu -= (w P)_v A_n^-1 (w P)_u; a view is PLACED when it has
+ *     a positive weight on a solved point; the rows and columns of the root and of the views that are not placed are taken out;
+ *   C = the eigenvector of the smallest eigenvalue (unit norm), C_root = 0;  X_n = A_n^-1 sum_v w P C_v;
+ *   when sum w depth < 0 over the weighted observations, C and X change sign (rel = X_n - C_v, depth = rel . d);
+ *   dist = |rel|, ang = |P rel| / dist; the next weight = good / (1 + (ang / (a_v 2^max(rounds - 2 - r, 0)))^2) with good = seen, solved,
+ *     depth > 0, dist > 1e-12 and, in the rounds r >= rounds - 2 only, ang < a_v.
+ * Outputs, device, all required: t (V,3) = -R_v C_v and centres (V,3) fp64, NaN for a view that is not placed; points (N,3) fp64, NaN
+ * where not solved in the last round; mask (V,N) uint8, weight > 0 after the last round; count (1) int32, the set mask entries;
+ * eigenvalues (2) fp64, the two smallest of the last round; status (1) int32: bit 0 = the second eigenvalue is not positive or not
+ * finite, bit 1 = a view was not placed in the last round, bit 2 = the root or all but one view is not placed.  On bit 0 or bit 2
+ * every output is NaN or 0.  t, centres, points, eigenvalues 16-byte aligned.
+ * workspace: roma_positions_workspace(V, N, M, offsets) bytes, 16-byte aligned, need not be initialised; the function (host only)
+ * stores the byte offsets of its 11 regions in offsets (may be NULL) — the state record, the view constants, the centres of two
+ * rounds, the edge records, the points of two rounds, the round-0 weights (a bit per view), the solved flags, the reduced matrix, its
+ * per-block partials, the partial depth sums — each a multiple of 256, and returns a negative code for a bad V, N or M.  With
+ * Ms = 3 V (3 V + 1) / 2 + V the partials take 8 Ms min(ceil(N / 64), 256) bytes and the points 53 N: no weight is ever stored, a
+ * weight is a function of the round before.
+ * 3 + 5 rounds launches on `stream`: init, vote, per round accumulate, reduce, solve, points, sign, then final.  The sums over the points
+ * are per-block partials (kept in LDS while a block walks its points) added in block order: no floating-point atomics (count uses an
+ * integer one), bitwise reproducible.  The eigen-solve is one workgroup: two-sided Jacobi in the round-robin order on at most 94 rows,
+ * the matrix and its eigenvectors in 141 KB of LDS.  No block waits for another, no host synchronisation: the call can be captured
+ * in a graph. */
+int roma_rotation_average(const double* R_rel, const int* pairs, const double* weights, int V, int M, int root, double sigma_deg, int iters,
+                          double* R, unsigned char* valid, double* residual, int* status, void* stream);
+long roma_positions_workspace(int V, int N, int M, long* offsets);
+int roma_global_positions(const float* const* obs, const float* to_px, const unsigned char* const* visible, long point_stride, const double* K,
+                          const double* R, const int* pairs, const double* t_rel, int V, int N, int M, int root, double threshold, int rounds,
+                          double* t, double* centres, double* points, unsigned char* mask, int* count, double* eigenvalues, int* status,
+                          void* workspace, long workspace_size, void* stream);
+
 /* Multi-view depth-map fusion (csrc/depth_fuse.hip): the depth maps of V posed views (2 <= V <= 32) checked against
  * one another by forward-backward reprojection, one owner chosen per surface point, and the owners compacted into one cloud.
  * Convention of roma_triangulate_nview: x_v ~ K_v (R_v X + t_v); pixel (row i, column j) of a map is at (u, v) = (j + 0.5, i + 0.5) in

@@ -131,13 +131,20 @@ SIGNATURES = {
     "roma_bundle_adjust": [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_uint,
                            ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_long, c_void_p],
+    "roma_rotation_average": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p],
+    "roma_positions_workspace": [c_int, c_int, c_int, c_void_p],
+    "roma_global_positions": [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                              ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
+                              c_void_p],
     "roma_depth_fuse_workspace": [c_int, c_long, c_void_p],
     "roma_depth_fuse": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_int, c_int, c_void_p,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
 }
 _RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long, "roma_essential_workspace": c_long,
              "roma_race_select_workspace": c_long, "roma_absolute_pose_workspace": c_long, "roma_similarity_workspace": c_long,
-             "roma_tracks_workspace": c_long, "roma_bundle_workspace": c_long, "roma_depth_fuse_workspace": c_long}
+             "roma_tracks_workspace": c_long, "roma_bundle_workspace": c_long, "roma_depth_fuse_workspace": c_long,
+             "roma_positions_workspace": c_long}
 
 _lib = None
 

@@ -68,6 +68,12 @@ system, sums in a fixed order, the decision to keep a step taken on the device â
 `triangulate_nview`, which each fit one kind while holding the other.  `reconstruction_error` is its metric: the worst rotation and
 centre error and the median point error after a closed-form similarity alignment of the camera centres.
 
+`average_rotations`, `global_positions` and `initialize_cameras` deliver the start that `bundle_adjust` asks for (csrc/
+motion_average.hip): the rotations of V views averaged over the pose graph of the pairwise `estimate_pose` results (spanning tree, then
+re-weighted least squares on the Lie algebra, L1 first), and under those rotations the camera centres and the points from the tracks â€”
+the linear known-rotation problem, the points eliminated one by one and the centres the smallest eigenvector of the reduced matrix,
+re-weighted from a majority vote of the pairwise translation directions.
+
 `fuse_depth_maps` is the dense counterpart (csrc/depth_fuse.hip): the depth maps of V posed views â€” `depth_from_warps` once per image â€”
 are checked against one another by forward-backward reprojection in fp64, every pixel keeps the views that agree with it and the mean
 of their depths, each surface point is owned by the lowest view that sees it, and the owners are compacted in a fixed order into one
@@ -1808,6 +1814,186 @@ def bundle_adjust(x, R, t, K, X, *, visible=None, threshold=2.0, iters=10, fixed
           "roma_bundle_adjust")
     res = BundleResult(Ro, to, Xo, mask.bool(), cost[1], cost[0], ints[1], ints[0], ints[2])
     return (res, {"status": ints[2]}) if return_info else res
+
+
+# ------------------------------------------------------------------------------------------------------------ motion averaging
+_POSITIONS_REGIONS = 11
+_MAX_EDGES = 4096
+
+
+class RotationAverage:
+    """What average_rotations returns, device tensors: R (V,3,3) fp64, NaN for a view the pose graph does not reach from the root; valid
+    (V) bool; residual_deg (M) fp64, the angle left on every edge under R (NaN for an edge that is not usable or not reached: an
+    outlier pair stands out by tens of degrees); status int32 (0, or 1: a pivot failed and R is the spanning-tree start)."""
+    __slots__ = ("R", "valid", "residual_deg", "status")
+
+    def __init__(self, R, valid, residual_deg, status):
+        self.R, self.valid, self.residual_deg, self.status = R, valid, residual_deg, status
+
+    def __repr__(self):
+        return f"RotationAverage(R={tuple(self.R.shape)}, edges={tuple(self.residual_deg.shape)}, device={self.R.device})"
+
+
+class GlobalPositions:
+    """What global_positions returns, device tensors: t (V,3) and centres (V,3) fp64, NaN for a view that is not placed; points (N,3) fp64,
+    NaN where a track is not solved; mask (V,N) bool, the observations that agree with the result; count int32, the set mask entries;
+    eigenvalues (2) fp64, the two smallest of the reduced matrix (their ratio says how well the centres are determined); status int32
+    (include/roma_hip.h: bit 0 and bit 2 mean no result, bit 1 that a view was not placed)."""
+    __slots__ = ("t", "centres", "points", "mask", "count", "eigenvalues", "status")
+
+    def __init__(self, t, centres, points, mask, count, eigenvalues, status):
+        self.t, self.centres, self.points, self.mask, self.count, self.eigenvalues, self.status = t, centres, points, mask, count, eigenvalues, status
+
+    def __repr__(self):
+        return f"GlobalPositions(t={tuple(self.t.shape)}, points={tuple(self.points.shape)}, device={self.t.device})"
+
+
+class CameraStart:
+    """What initialize_cameras returns: R (V,3,3), t (V,3), points (N,3) fp64, mask (V,N) bool, valid (V) bool, and the two status words
+    rotation_status, position_status (int32) â€” ready for bundle_adjust(x, R, t, K, points, visible=mask, threshold=8.0)."""
+    __slots__ = ("R", "t", "points", "mask", "valid", "rotation_status", "position_status")
+
+    def __init__(self, R, t, points, mask, valid, rotation_status, position_status):
+        self.R, self.t, self.points, self.mask, self.valid = R, t, points, mask, valid
+        self.rotation_status, self.position_status = rotation_status, position_status
+
+    def __repr__(self):
+        return f"CameraStart(R={tuple(self.R.shape)}, points={tuple(self.points.shape)}, device={self.R.device})"
+
+
+def _edges(pairs, M, device):
+    """(M,2) view indices, tensor or numpy -> contiguous int32 on the device"""
+    if not torch.is_tensor(pairs):
+        pairs = torch.as_tensor(pairs, dtype=torch.int32).to(device)
+    _need_gpu(pairs)
+    if pairs.shape != (M, 2) or pairs.is_floating_point():
+        raise ValueError(f"pairs {tuple(pairs.shape)} {pairs.dtype}: expected integer ({M},2)")
+    return pairs.to(torch.int32).contiguous()
+
+
+def _view_index(root, V):
+    root = int(root)
+    if not 0 <= root < V:
+        raise ValueError(f"root must be one of the {V} views, got {root}")
+    return root
+
+
+def average_rotations(R_rel, pairs, V, *, weights=None, root=0, sigma_deg=5.0, iters=12):
+    """Global rotations of V views (2 to 32) from the M pairwise rotations of a pose graph (csrc/motion_average.hip, one launch of one
+    workgroup): the maximum-weight spanning tree from `root` as the start, then `iters` rounds (0 to 50) of re-weighted least squares on
+    the Lie algebra â€” the first half with L1 weights, which gets out of a tree that contains an outlier edge, the second half with
+    Geman-McClure weights at sigma_deg â€” each a weighted graph Laplacian solved by Cholesky.
+    R_rel: (M,3,3), pairs: (M,2) with pairs[m] = (a, b) and X_b = R_rel[m] X_a + t (estimate_pose's convention), 1 <= M <= 4096; weights:
+    (M) or None (all 1), e.g. the inlier count of the pair's RANSAC.  Returns a RotationAverage; R[root] = I, and R follows
+    triangulate_nview / bundle_adjust: x_v ~ K_v (R_v X + t_v).  No host synchronisation: the call can be captured in a graph."""
+    V, iters, sigma = int(V), int(iters), float(sigma_deg)
+    if not 2 <= V <= _MAX_VIEWS:
+        raise ValueError(f"{V} views: 2 to {_MAX_VIEWS} are supported")
+    root = _view_index(root, V)
+    if not 0 <= iters <= 50:
+        raise ValueError(f"iters must be in [0, 50], got {iters}")
+    if not 0.0 < sigma < 1e18:
+        raise ValueError(f"sigma_deg must be positive, got {sigma_deg}")
+    _need_gpu(R_rel, weights)
+    if R_rel.dim() != 3 or R_rel.shape[1:] != (3, 3) or not R_rel.is_floating_point():
+        raise ValueError(f"R_rel {tuple(R_rel.shape)} {R_rel.dtype}: expected floating-point (M,3,3)")
+    M = R_rel.shape[0]
+    if not 1 <= M <= _MAX_EDGES:
+        raise ValueError(f"{M} edges: 1 to {_MAX_EDGES} are supported")
+    dev = R_rel.device
+    pr = _edges(pairs, M, dev)
+    if weights is not None and weights.shape != (M,):
+        raise ValueError(f"weights {tuple(weights.shape)}: expected ({M},)")
+    Rr = R_rel.to(torch.float64).contiguous()
+    wt = None if weights is None else weights.to(torch.float64).contiguous()
+    R = torch.empty((V, 3, 3), dtype=torch.float64, device=dev)
+    valid = torch.empty((V,), dtype=torch.uint8, device=dev)
+    res = torch.empty((M,), dtype=torch.float64, device=dev)
+    status = torch.empty((1,), dtype=torch.int32, device=dev)
+    check(_lib.load().roma_rotation_average(Rr.data_ptr(), pr.data_ptr(), None if wt is None else wt.data_ptr(), V, M, root, sigma, iters,
+                                            R.data_ptr(), valid.data_ptr(), res.data_ptr(), status.data_ptr(), _stream()),
+          "roma_rotation_average")
+    return RotationAverage(R, valid.bool(), torch.rad2deg(res), status[0])
+
+
+def positions_workspace_layout(V, N, M):
+    """-> (bytes, offsets of the 11 regions) of roma_positions_workspace; raises ValueError on a bad shape"""
+    off = (ctypes.c_long * _POSITIONS_REGIONS)()
+    need = _lib.load().roma_positions_workspace(int(V), int(N), int(M), ctypes.cast(off, ctypes.c_void_p))
+    if need < 0:
+        check(int(need), "roma_positions_workspace")
+    return int(need), list(off)
+
+
+def global_positions(x, R, K, pairs, t_rel, *, visible=None, threshold=4.0, rounds=4, root=0):
+    """Camera centres and points of one reconstruction under KNOWN rotations (csrc/motion_average.hip): with R from average_rotations the
+    problem is linear â€” every observation asks its point to lie on the ray from its camera â€”, the points are eliminated one by one and
+    the centres are the smallest eigenvector of the reduced 3 V x 3 V matrix (the Schur pattern of bundle_adjust), re-weighted over
+    `rounds` rounds (2 to 8).  The first weights are a majority vote of the pairwise translation directions: an observation counts when
+    at least half of the edges that join its view to another view of its track agree with it.
+    x: (V,N,2) pixels and visible (V,N), read exactly as bundle_adjust reads them (`Tracks.x`, `Tracks.visible` as they come), 3 <= V <=
+    32; R: (V,3,3), NaN for a view that has none; K: (3,3) or (V,3,3); pairs (M,2) and t_rel (M,3): the edges, of which only the
+    direction of t_rel is used (X_b = R_rel X_a + t_rel); threshold in pixels; root: the view at the origin.  The scale is fixed by
+    sum |C_v|^2 = 1.  Returns a GlobalPositions.  Sums in a fixed order, no floating-point atomics: bitwise reproducible; no host
+    synchronisation: the call can be captured in a graph."""
+    thr, rounds = float(threshold), int(rounds)
+    if not 0.0 < thr < 1e18:
+        raise ValueError(f"threshold must be positive pixels, got {threshold}")
+    if not 2 <= rounds <= 8:
+        raise ValueError(f"rounds must be in [2, 8], got {rounds}")
+    _need_gpu(x, visible)
+    if x.dim() != 3 or x.shape[-1] != 2 or not x.is_floating_point():
+        raise ValueError(f"expected floating-point observations (V,N,2), got {tuple(x.shape)} {x.dtype}")
+    V, N = x.shape[0], x.shape[1]
+    if not 3 <= V <= _MAX_VIEWS:
+        raise ValueError(f"{V} views: 3 to {_MAX_VIEWS} are supported")
+    if N < 1:
+        raise ValueError("no points")
+    root = _view_index(root, V)
+    if visible is not None and visible.shape != (V, N):
+        raise ValueError(f"visible {tuple(visible.shape)} does not match the observations {tuple(x.shape)}")
+    dev = x.device
+    if not torch.is_tensor(t_rel):
+        t_rel = torch.as_tensor(t_rel, dtype=torch.float64).to(dev)
+    _need_gpu(t_rel)
+    if t_rel.dim() != 2 or t_rel.shape[1] != 3:
+        raise ValueError(f"t_rel {tuple(t_rel.shape)}: expected (M,3)")
+    M = t_rel.shape[0]
+    if not 1 <= M <= _MAX_EDGES:
+        raise ValueError(f"{M} edges: 1 to {_MAX_EDGES} are supported")
+    pr = _edges(pairs, M, dev)
+    tr = t_rel.to(torch.float64).contiguous()
+    xs = x.to(torch.float32).contiguous()
+    vis = None if visible is None else visible.to(torch.uint8).contiguous()
+    Rp, _ = _poses(R, torch.zeros((V, 3), dtype=torch.float64, device=dev), V, dev)
+    Kp = _intrinsics(K, V, dev, "K")
+    need, _ = positions_workspace_layout(V, N, M)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    t, centres, points, lam = torch.empty((V, 3), **f64), torch.empty((V, 3), **f64), torch.empty((N, 3), **f64), torch.empty((2,), **f64)
+    mask = torch.empty((V, N), dtype=torch.uint8, device=dev)
+    ints = torch.empty((2,), dtype=torch.int32, device=dev)                       # count, status
+    obs_tab = (ctypes.c_void_p * V)(*[xs.data_ptr() + 8 * N * v for v in range(V)])
+    vis_tab = None if vis is None else (ctypes.c_void_p * V)(*[vis.data_ptr() + N * v for v in range(V)])
+    check(_lib.load().roma_global_positions(ctypes.cast(obs_tab, ctypes.c_void_p), None, None if vis_tab is None else ctypes.cast(vis_tab, ctypes.c_void_p),
+                                            2, Kp.data_ptr(), Rp.data_ptr(), pr.data_ptr(), tr.data_ptr(), V, N, M, root, thr, rounds, t.data_ptr(),
+                                            centres.data_ptr(), points.data_ptr(), mask.data_ptr(), ints.data_ptr(), lam.data_ptr(),
+                                            ints.data_ptr() + 4, ws.data_ptr(), need, _stream()),
+          "roma_global_positions")
+    return GlobalPositions(t, centres, points, mask.bool(), ints[0], lam, ints[1])
+
+
+def initialize_cameras(x, K, pairs, R_rel, t_rel, *, visible=None, weights=None, threshold=4.0, root=0):
+    """The V cameras and the points of a reconstruction from its tracks and the pairwise poses of its image pairs â€” average_rotations,
+    then global_positions under those rotations: the start that bundle_adjust asks for.  x, visible: `Tracks.x`, `Tracks.visible`; K:
+    (3,3) or (V,3,3); pairs (M,2), R_rel (M,3,3), t_rel (M,3): what estimate_pose returned for pairs[m] = (a, b); weights: (M), e.g.
+    the pairs' inlier counts.  Returns a CameraStart: R, t, points, mask, valid and both status words.  The frame is that of `root`
+    (R = I, t = 0) and the scale that of sum |C_v|^2 = 1."""
+    if x.dim() != 3:
+        raise ValueError(f"expected observations (V,N,2), got {tuple(x.shape)}")
+    rot = average_rotations(R_rel, pairs, x.shape[0], weights=weights, root=root)
+    pos = global_positions(x, rot.R, K, pairs, t_rel, visible=visible, threshold=threshold, root=root)
+    return CameraStart(rot.R, pos.t, pos.points, pos.mask, rot.valid, rot.status, pos.status)
 
 
 # ------------------------------------------------------------------------------------------------------------ depth-map fusion
