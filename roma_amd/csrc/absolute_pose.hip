@@ -68,30 +68,6 @@ __device__ __forceinline__ Cam load_cam(const double* K) { return Cam{K[0], K[1]
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
-// Gram-Schmidt on the rows: r0, r1 made orthogonal to r0, r2 = r0 x r1
-__device__ __forceinline__ void orthonormalise(const double* X, double* Rc) {
-  const double i0 = 1.0 / sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Rc[i] = X[i] * i0;
-  const double d = Rc[0] * X[3] + Rc[1] * X[4] + Rc[2] * X[5];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Rc[3 + i] = X[3 + i] - d * Rc[i];
-  const double i1 = 1.0 / sqrt(Rc[3] * Rc[3] + Rc[4] * Rc[4] + Rc[5] * Rc[5]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Rc[3 + i] *= i1;
-  cross3(Rc, Rc + 3, Rc + 6);
-}
-
-// out = [v]x A (3 x 3, row major)
-__device__ __forceinline__ void skew_times(const double* v, const double* A, double* out) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    out[c] = v[1] * A[6 + c] - v[2] * A[3 + c];
-    out[3 + c] = v[2] * A[c] - v[0] * A[6 + c];
-    out[6 + c] = v[0] * A[3 + c] - v[1] * A[c];
-  }
-}
-
 // ------------------------------------------------------------------------------------------- residual, Jacobian, step (fp64)
 // One match under (R, t): squared error e in pixels, depth z, residual (ru, rv), Jacobian by (w, dt).  Nothing is guarded: a row that
 // is not finite, or z = 0, gives NaN / inf, which the callers' comparisons turn down.
@@ -150,7 +126,7 @@ __device__ __forceinline__ void ap_apply_step(const double* R, const double* t, 
   skew_times(w, KR, KKR);
 #pragma unroll
   for (int i = 0; i < 9; ++i) X[i] = R[i] + A * KR[i] + B * KKR[i];
-  orthonormalise(X, Rc);
+  orthonormalise_rows(X, Rc);
 #pragma unroll
   for (int i = 0; i < 3; ++i) tc[i] = t[i] + delta[3 + i];
 }
@@ -448,7 +424,7 @@ __global__ __launch_bounds__(P3P_THREADS) void p3p_kernel(const double* __restri
           for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int c = 0; c < 3; ++c) Rm[3 * r + c] = g1[r] * Ai[c] + g2[r] * Ai[3 + c] + gc[r] * Ai[6 + c];
-          orthonormalise(Rm, R);
+          orthonormalise_rows(Rm, R);
 #pragma unroll
           for (int r = 0; r < 3; ++r) tt[r] = Y[0][r] - (R[3 * r] * Xs[0][0] + R[3 * r + 1] * Xs[0][1] + R[3 * r + 2] * Xs[0][2]);
 #pragma unroll 1

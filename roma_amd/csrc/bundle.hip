@@ -35,21 +35,14 @@
 // Every launch after init reads `finished` first and returns at once when it is set.  No block waits for another block: no flags, no
 // spin loops, no cooperative grid; every loop has a trip count fixed by (V, N) before it starts.  `count` is summed with an integer
 // atomic (it commutes).  No host synchronisation: the call can be captured in a graph.
-#include "twoview_math.h"
+#include "multiview.h"
 
 namespace roma {
 namespace {
 
-constexpr int MAX_VIEWS = 32, CHUNK = 64, MAX_PARTIALS = 256, POINT_THREADS = 256, SOLVE_THREADS = 256, REGIONS = 11;
+constexpr int CHUNK = 64, MAX_PARTIALS = 256, POINT_THREADS = 256, SOLVE_THREADS = 256, REGIONS = 11;
 constexpr double LAMBDA0 = 1e-3, LAMBDA_MIN = 1e-10, ACCEPT_REL = 1e-12;
 constexpr int STATUS_PIVOT = 1, STATUS_NO_FREE_VIEW = 2, STATUS_NOT_FINITE = 4;
-
-// kernel arguments by value (triangulate_nview's ViewTable)
-struct ObsTable {
-  const float* obs[MAX_VIEWS];
-  const unsigned char* vis[MAX_VIEWS];
-  float px[MAX_VIEWS][4];          // sx, ox, sy, oy
-};
 
 struct State {
   double lambda, cost, cost0;
@@ -85,18 +78,6 @@ struct Prm {
   double thr2;
   unsigned fixed;
 };
-
-__host__ __device__ inline int tri(int n) { return n * (n + 1) / 2; }
-
-__device__ __forceinline__ bool load_px(const ObsTable& tab, int v, long n, long stride, double& x, double& y) {
-  const float2 q = *reinterpret_cast<const float2*>(tab.obs[v] + n * stride);
-  const unsigned char* vis = tab.vis[v];
-  const bool see = vis ? vis[n] != 0 : true;
-  const float fx = q.x * tab.px[v][0] + tab.px[v][1], fy = q.y * tab.px[v][2] + tab.px[v][3];
-  x = (double)fx;
-  y = (double)fy;
-  return see && isfinite(fx) && isfinite(fy);
-}
 
 // q = R X + t, the pixel residual and its square
 struct Proj {
@@ -190,10 +171,10 @@ __device__ __forceinline__ PointEq point_equations(const ObsTable& tab, const Vi
 #pragma unroll 1
   for (int v = 0; v < V; ++v) {
     const ViewL& c = view[v];
-    double px, py;
+    float px, py;
     const bool seen = load_px(tab, v, n, stride, px, py);
     if (!(seen && fin && c.ok != 0.0)) continue;
-    const Proj p = project(c.k, c.R, c.t, X, px, py);
+    const Proj p = project(c.k, c.R, c.t, X, (double)px, (double)py);
     const bool w = p.q2 > 0.0 && p.e < thr2;
     o.observed |= 1u << v;
     o.cost += w ? p.e : thr2;
@@ -218,12 +199,6 @@ __device__ __forceinline__ PointEq point_equations(const ObsTable& tab, const Vi
   return o;
 }
 
-__device__ __forceinline__ void sym3_times(const double* s, const double* x, double* y) {
-  y[0] = s[0] * x[0] + s[1] * x[1] + s[2] * x[2];
-  y[1] = s[1] * x[0] + s[3] * x[1] + s[4] * x[2];
-  y[2] = s[2] * x[0] + s[4] * x[1] + s[5] * x[2];
-}
-
 // t + R c0: the translation in the frame centred at c0
 __device__ __forceinline__ double centred_t(const double* R, const double* t, const double* c0, int j) {
   return t[j] + (R[3 * j] * c0[0] + R[3 * j + 1] * c0[1] + R[3 * j + 2] * c0[2]);
@@ -240,7 +215,7 @@ __global__ __launch_bounds__(CHUNK) void bundle_init_kernel(Ws ws, Prm prm, cons
     const double* Rv = R + 9 * tid;
     const double* tv = t + 3 * tid;
     double ki[5];
-    bool ok = invert_k(Kv, ki) && Kv[3] == 0.0 && Kv[6] == 0.0 && Kv[7] == 0.0 && isfinite(Kv[8]);
+    bool ok = invert_k(Kv, ki) && upper_triangular(Kv);
 #pragma unroll
     for (int i = 0; i < 9; ++i) ok = ok && isfinite(Rv[i]);
 #pragma unroll
@@ -390,9 +365,9 @@ __global__ __launch_bounds__(CHUNK) void bundle_accumulate_kernel(ObsTable tab, 
       const int held_i = s_held[i];
       if (tid < V && ((act >> tid) & 1u)) {
         const ViewL& c = s_view[tid];
-        double px, py;
+        float px, py;
         load_px(tab, tid, ni, prm.point_stride, px, py);
-        const Proj p = project(c.k, c.R, c.t, s_pt[i], px, py);
+        const Proj p = project(c.k, c.R, c.t, s_pt[i], (double)px, (double)py);
         double Jc[2][6], Jp[2][3];
         jacobians(c.k, c.R, p, Jc, Jp);
         const int r0 = 6 * tid;
@@ -448,11 +423,7 @@ __global__ __launch_bounds__(CHUNK) void bundle_accumulate_kernel(ObsTable tab, 
 
 __global__ __launch_bounds__(POINT_THREADS) void bundle_reduce_kernel(Ws ws, Prm prm) {
   if (ws.st->finished) return;
-  const int e = blockIdx.x * POINT_THREADS + threadIdx.x;
-  if (e >= prm.M) return;
-  double s = 0.0;
-  for (int p = 0; p < prm.P; ++p) s += ws.part[(size_t)p * prm.M + e];
-  ws.sys[e] = s;
+  reduce_partials(ws.part, ws.sys, prm.M, prm.P, blockIdx.x * POINT_THREADS + threadIdx.x);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- solve
@@ -546,7 +517,7 @@ __global__ __launch_bounds__(POINT_THREADS) void bundle_propose_kernel(ObsTable 
       }
       double A, B;
       so3_exp_series(th2, A, B, So3Literals());
-      // E = I + A [w]x + B [w]x^2
+      // E = I + A [w]x + B [w]x^2.  The step and the Gram-Schmidt are written out here: profiles/multiview_shared_code_micro.txt
       const double Kx[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
       double E[9];
 #pragma unroll
@@ -657,12 +628,7 @@ long layout(int V, int N, long* off) {
   const long P = std::min<long>(((long)N + CHUNK - 1) / CHUNK, MAX_PARTIALS);
   const long bytes[REGIONS] = {(long)sizeof(State), (long)sizeof(ViewK) * MAX_VIEWS, 8L * (3 + 7 * MAX_VIEWS), (long)sizeof(ViewP) * MAX_VIEWS,
                                (long)sizeof(ViewP) * MAX_VIEWS, 24L * N, 24L * N, 2L * N, 8 * M, 8 * M * P, 8 * P};
-  long at = 0;
-  for (int i = 0; i < REGIONS; ++i) {
-    if (off) off[i] = at;
-    at += (bytes[i] + 255) / 256 * 256;
-  }
-  return at;
+  return layout_regions(bytes, REGIONS, off);
 }
 
 int check_shape(const char* fn, int V, int N) {
@@ -703,19 +669,10 @@ extern "C" int roma_bundle_adjust(const float* const* obs, const float* to_px, c
   ROMA_REQUIRE(aligned16(workspace) && aligned16(K) && aligned16(R_in) && aligned16(t_in) && aligned16(X_in) && aligned16(R) && aligned16(t) &&
                    aligned16(X) && aligned16(cost),
                ROMA_E_ALIGN, "roma_bundle_adjust: workspace, K, R_in, t_in, X_in, R, t, X and cost must be 16-byte aligned");
-  ROMA_REQUIRE((reinterpret_cast<uintptr_t>(count) & 3) == 0 && (reinterpret_cast<uintptr_t>(steps) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(status) & 3) == 0,
-               ROMA_E_ALIGN, "roma_bundle_adjust: count, steps and status must be 4-byte aligned");
+  ROMA_REQUIRE(aligned4(count) && aligned4(steps) && aligned4(status), ROMA_E_ALIGN,
+               "roma_bundle_adjust: count, steps and status must be 4-byte aligned");
   ObsTable tab;
-  for (int v = 0; v < MAX_VIEWS; ++v) {
-    const int u = v < V ? v : 0;
-    ROMA_REQUIRE(obs[u] != nullptr, ROMA_E_ARG, "roma_bundle_adjust: null pointer (observations of view %d)", u);
-    ROMA_REQUIRE((reinterpret_cast<uintptr_t>(obs[u]) & 7) == 0, ROMA_E_ALIGN, "roma_bundle_adjust: the observations of view %d must be 8-byte aligned",
-                 u);
-    tab.obs[v] = obs[u];
-    tab.vis[v] = visible ? visible[u] : nullptr;
-    for (int i = 0; i < 4; ++i) tab.px[v][i] = to_px ? to_px[4 * u + i] : ((i & 1) ? 0.f : 1.f);
-  }
+  if (int rc = fill_obs_table("roma_bundle_adjust", obs, to_px, visible, V, tab)) return rc;
   Prm prm;
   prm.V = V; prm.N = N; prm.n = 6 * V; prm.M = tri(prm.n) + 2 * prm.n + V;
   prm.P = std::min((N + CHUNK - 1) / CHUNK, MAX_PARTIALS);

@@ -33,7 +33,7 @@
 // Gather addressing (as sample_depth in depth_warp.hip).  A projection may be NaN, inf or 1e30, so the un-normalised coordinate is
 // range-checked IN FLOATING POINT with a negated conjunction (NaN fails it) before anything is converted to an integer, and every tap
 // index is checked against the map again.  No address is formed from an unchecked value; the ownership lookup does the same.
-#include "common.h"
+#include "multiview.h"
 
 #include <climits>
 
@@ -41,7 +41,7 @@ namespace roma {
 namespace {
 
 constexpr int THREADS = 256, ITEMS = 4, PIXELS_PER_BLOCK = THREADS * ITEMS, WAVES = THREADS / 64;
-constexpr int MAX_VIEWS = 32, MAX_SIDE = 32768, SCAN_THREADS = 1024;
+constexpr int MAX_SIDE = 32768, SCAN_THREADS = 1024;
 
 // kernel arguments by value
 struct FuseTable {
@@ -290,6 +290,7 @@ __global__ __launch_bounds__(THREADS) void fuse_ownership_kernel(FuseTable tab, 
 }
 
 // ------------------------------------------------------------------------------------------------------------ scan
+// (the loop of tracks.hip's tracks_scan_kernel, written out in both: profiles/multiview_shared_code_micro.txt)
 // one workgroup: block_counts[b][0] becomes the number of flagged pixels in the blocks before b; counts = the totals and a status of 0
 __global__ __launch_bounds__(SCAN_THREADS) void fuse_scan_kernel(unsigned* __restrict__ block_counts, int blocks, int* __restrict__ counts) {
   __shared__ unsigned s_wave[SCAN_THREADS / 64];
@@ -435,7 +436,7 @@ extern "C" int roma_depth_fuse(const float* const* depths, const int* dims, cons
     ROMA_REQUIRE(H >= 1 && H <= MAX_SIDE && W >= 1 && W <= MAX_SIDE, ROMA_E_SHAPE, "roma_depth_fuse: bad shape map %d is %dx%d (sides 1 to %d)",
                  v, H, W, MAX_SIDE);
     ROMA_REQUIRE(depths[v] != nullptr, ROMA_E_ARG, "roma_depth_fuse: null pointer (depth map of view %d)", v);
-    ROMA_REQUIRE((reinterpret_cast<uintptr_t>(depths[v]) & 3) == 0, ROMA_E_ALIGN, "roma_depth_fuse: the depth map of view %d must be 4-byte aligned",
+    ROMA_REQUIRE(aligned4(depths[v]), ROMA_E_ALIGN, "roma_depth_fuse: the depth map of view %d must be 4-byte aligned",
                  v);
     const long n = (long)H * W, nb = (n + PIXELS_PER_BLOCK - 1) / PIXELS_PER_BLOCK;
     tab.depth[v] = depths[v];

@@ -261,7 +261,6 @@ __global__ __launch_bounds__(64) void dense_metrics_finish_kernel(const Partial*
 }
 
 inline bool side_ok(int v) { return v >= 1 && v <= MAX_SIDE; }
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace
 }  // namespace roma

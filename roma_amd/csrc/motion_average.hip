@@ -32,15 +32,17 @@
 
 #pragma clang fp contract(off)
 
+// after the pragma: the functions of multiview.h are this file's own code and must round as it does (no multiply fused with an add);
+// before it they would be contracted, and the results are pinned to tests/motion_ref.py bit for bit
+#include "multiview.h"
+
 namespace roma {
 namespace {
 
-constexpr int MAX_VIEWS = 32, MAX_EDGES = 4096, CHUNK = 64, MAX_PARTIALS = 256, POINT_THREADS = 256, MAX_POINT_BLOCKS = 1024, SOLVE_THREADS = 1024;
+constexpr int MAX_EDGES = 4096, CHUNK = 64, MAX_PARTIALS = 256, POINT_THREADS = 256, MAX_POINT_BLOCKS = 1024, SOLVE_THREADS = 1024;
 constexpr int ROT_SLICES = 4, ROT_THREADS = MAX_VIEWS * ROT_SLICES, ROT_LD = 36, SWEEPS = 16, REGIONS = 11;
 constexpr int ROT_STATUS_PIVOT = 1;
 constexpr int STATUS_EIGEN = 1, STATUS_UNPLACED = 2, STATUS_TOO_FEW = 4;
-
-__host__ __device__ inline int tri(int n) { return n * (n + 1) / 2; }
 
 // ================================================================================================================= rotations
 // r = log(Rb^T Rrel Ra) and its length
@@ -62,7 +64,8 @@ __device__ __forceinline__ double edge_residual(const double* Ra, const double* 
   return sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
 }
 
-// R <- rows of (R exp([w]x)) made orthonormal (the series and the Gram-Schmidt of the other refinements)
+// R <- rows of (R exp([w]x)) made orthonormal.  The step matrix and the Gram-Schmidt (twoview_math.h's orthonormalise_rows) are written
+// out: here they must not be contracted, and the header is included before the pragma (profiles/multiview_shared_code_isa.txt)
 __device__ __forceinline__ void rotate_right(double* R, const double* delta) {
   double w[3] = {delta[0], delta[1], delta[2]};
   double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
@@ -264,13 +267,6 @@ __global__ __launch_bounds__(ROT_THREADS) void rotation_average_kernel(const dou
 }
 
 // ================================================================================================================= positions
-// kernel arguments by value (bundle.hip's ObsTable)
-struct ObsTable {
-  const float* obs[MAX_VIEWS];
-  const unsigned char* vis[MAX_VIEWS];
-  float px[MAX_VIEWS][4];          // sx, ox, sy, oy
-};
-
 struct State {
   int finished, status, pad0, pad1;
   double sign[2];                  // of round r at r & 1
@@ -305,16 +301,6 @@ struct Prm {
   int V, N, M, P, PB, Msys, root, rounds;   // Msys = tri(3 V) + V: the lower triangle, then the weighted observations per view
   long point_stride;
 };
-
-// the pixel of (v, n), NaN where not seen
-__device__ __forceinline__ float2 load_px(const ObsTable& tab, int v, long n, long stride) {
-  const float2 q = *reinterpret_cast<const float2*>(tab.obs[v] + n * stride);
-  const unsigned char* vis = tab.vis[v];
-  const bool see = vis ? vis[n] != 0 : true;
-  const float fx = q.x * tab.px[v][0] + tab.px[v][1], fy = q.y * tab.px[v][2] + tab.px[v][3];
-  const float nanf = __builtin_nanf("");
-  return see && isfinite(fx) && isfinite(fy) ? make_float2(fx, fy) : make_float2(nanf, nanf);
-}
 
 // d = R^T h / |h|, h = K^-1 (x, y, 1); false when the pixel is not seen or the view not usable
 __device__ __forceinline__ bool bearing(const ViewC& c, float2 px, double* d) {
@@ -366,12 +352,6 @@ __device__ __forceinline__ bool inverse3(const double* a, double* inv) {
   return det > 1e-12 * tr * tr * tr;
 }
 
-__device__ __forceinline__ void sym3_times(const double* s, const double* x, double* y) {
-  y[0] = s[0] * x[0] + s[1] * x[1] + s[2] * x[2];
-  y[1] = s[1] * x[0] + s[3] * x[1] + s[4] * x[2];
-  y[2] = s[2] * x[0] + s[4] * x[1] + s[5] * x[2];
-}
-
 // --------------------------------------------------------------------------------------------------------------------- init
 __global__ __launch_bounds__(POINT_THREADS) void positions_init_kernel(Ws ws, Prm prm, const double* __restrict__ K, const double* __restrict__ R,
                                                                        const int* __restrict__ pairs, const double* __restrict__ t_rel,
@@ -390,7 +370,7 @@ __global__ __launch_bounds__(POINT_THREADS) void positions_init_kernel(Ws ws, Pr
       const double fx = Kv[0], sk = Kv[1], cx = Kv[2], fy = Kv[4], cy = Kv[5], dk = fx * fy;
       c.ki[0] = 1.0 / fx; c.ki[1] = -sk / dk; c.ki[2] = (sk * cy - cx * fy) / dk; c.ki[3] = 1.0 / fy; c.ki[4] = -cy / fy;
       ok = isfinite(fx) && isfinite(sk) && isfinite(cx) && isfinite(fy) && isfinite(cy) && dk != 0.0 && isfinite(1.0 / dk);
-      ok = ok && Kv[3] == 0.0 && Kv[6] == 0.0 && Kv[7] == 0.0 && isfinite(Kv[8]);
+      ok = ok && upper_triangular(Kv);
 #pragma unroll
       for (int i = 0; i < 9; ++i) { ok = ok && isfinite(Rv[i]); c.R[i] = Rv[i]; }
       c.ang = threshold / sqrt(fabs(Kv[0] * Kv[4]));
@@ -571,11 +551,7 @@ __global__ __launch_bounds__(CHUNK) void positions_accumulate_kernel(ObsTable ta
 
 __global__ __launch_bounds__(POINT_THREADS) void positions_reduce_kernel(Ws ws, Prm prm) {
   if (ws.st->finished) return;
-  const int e = blockIdx.x * POINT_THREADS + threadIdx.x;
-  if (e >= prm.Msys) return;
-  double s = 0.0;
-  for (int p = 0; p < prm.P; ++p) s += ws.part[(size_t)p * prm.Msys + e];
-  ws.sys[e] = s;
+  reduce_partials(ws.part, ws.sys, prm.Msys, prm.P, blockIdx.x * POINT_THREADS + threadIdx.x);
 }
 
 // -------------------------------------------------------------------------------------------------------------------- solve
@@ -821,12 +797,7 @@ long layout(int V, int N, int M, long* off) {
   const long P = std::min<long>(((long)N + CHUNK - 1) / CHUNK, MAX_PARTIALS);
   const long bytes[REGIONS] = {(long)sizeof(State), (long)sizeof(ViewC) * MAX_VIEWS, 8L * 6 * MAX_VIEWS + 4L * MAX_VIEWS, (long)sizeof(EdgeRec) * M,
                                24L * N, 24L * N, 4L * N, 1L * N, 8 * Msys, 8 * Msys * P, 8L * MAX_POINT_BLOCKS};
-  long at = 0;
-  for (int i = 0; i < REGIONS; ++i) {
-    if (off) off[i] = at;
-    at += (bytes[i] + 255) / 256 * 256;
-  }
-  return at;
+  return layout_regions(bytes, REGIONS, off);
 }
 
 int check_shape(const char* fn, int V, int N, int M) {
@@ -849,9 +820,9 @@ extern "C" int roma_rotation_average(const double* R_rel, const int* pairs, cons
   ROMA_REQUIRE(root >= 0 && root < V, ROMA_E_ARG, "roma_rotation_average: root=%d is not one of the V=%d views", root, V);
   ROMA_REQUIRE(sigma_deg > 0.0 && sigma_deg < 1e18, ROMA_E_ARG, "roma_rotation_average: sigma_deg must be positive, got %g", sigma_deg);
   ROMA_REQUIRE(iters >= 0 && iters <= 50, ROMA_E_ARG, "roma_rotation_average: iters must be in [0, 50], got %d", iters);
-  ROMA_REQUIRE(aligned16(R_rel) && aligned16(R) && (reinterpret_cast<uintptr_t>(residual) & 7) == 0 && (weights == nullptr || (reinterpret_cast<uintptr_t>(weights) & 7) == 0),
-               ROMA_E_ALIGN, "roma_rotation_average: R_rel and R must be 16-byte aligned, weights and residual 8-byte aligned");
-  ROMA_REQUIRE((reinterpret_cast<uintptr_t>(pairs) & 3) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0, ROMA_E_ALIGN,
+  ROMA_REQUIRE(aligned16(R_rel) && aligned16(R) && aligned8(residual) && (weights == nullptr || aligned8(weights)), ROMA_E_ALIGN,
+               "roma_rotation_average: R_rel and R must be 16-byte aligned, weights and residual 8-byte aligned");
+  ROMA_REQUIRE(aligned4(pairs) && aligned4(status), ROMA_E_ALIGN,
                "roma_rotation_average: pairs and status must be 4-byte aligned");
   const double sigma = sigma_deg * 3.14159265358979323846 / 180.0;
   hipLaunchKernelGGL(rotation_average_kernel, dim3(1), dim3(ROT_THREADS), 0, static_cast<hipStream_t>(stream), R_rel, pairs, weights, V, M, root,
@@ -883,19 +854,10 @@ extern "C" int roma_global_positions(const float* const* obs, const float* to_px
   ROMA_REQUIRE(aligned16(workspace) && aligned16(K) && aligned16(R) && aligned16(t_rel) && aligned16(t) && aligned16(centres) && aligned16(points) &&
                    aligned16(eigenvalues),
                ROMA_E_ALIGN, "roma_global_positions: workspace, K, R, t_rel, t, centres, points and eigenvalues must be 16-byte aligned");
-  ROMA_REQUIRE((reinterpret_cast<uintptr_t>(count) & 3) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(pairs) & 3) == 0,
-               ROMA_E_ALIGN, "roma_global_positions: pairs, count and status must be 4-byte aligned");
+  ROMA_REQUIRE(aligned4(count) && aligned4(status) && aligned4(pairs), ROMA_E_ALIGN,
+               "roma_global_positions: pairs, count and status must be 4-byte aligned");
   ObsTable tab;
-  for (int v = 0; v < MAX_VIEWS; ++v) {
-    const int u = v < V ? v : 0;
-    ROMA_REQUIRE(obs[u] != nullptr, ROMA_E_ARG, "roma_global_positions: null pointer (observations of view %d)", u);
-    ROMA_REQUIRE((reinterpret_cast<uintptr_t>(obs[u]) & 7) == 0, ROMA_E_ALIGN,
-                 "roma_global_positions: the observations of view %d must be 8-byte aligned", u);
-    tab.obs[v] = obs[u];
-    tab.vis[v] = visible ? visible[u] : nullptr;
-    for (int i = 0; i < 4; ++i) tab.px[v][i] = to_px ? to_px[4 * u + i] : ((i & 1) ? 0.f : 1.f);
-  }
+  if (int rc = fill_obs_table("roma_global_positions", obs, to_px, visible, V, tab)) return rc;
   Prm prm;
   prm.V = V; prm.N = N; prm.M = M; prm.root = root; prm.rounds = rounds;
   prm.Msys = tri(3 * V) + V;

@@ -43,16 +43,6 @@ constexpr int RP_COST = 20, RP_COUNT = 21;
 constexpr int RP_MIN_MATCHES = 5;
 constexpr double RP_LAMBDA0 = 1e-3, RP_LAMBDA_MIN = 1e-10, RP_ACCEPT_REL = 1e-12;
 
-// out = [v]x A (3 x 3, row major)
-__device__ __forceinline__ void skew_mul(const double* v, const double* A, double* out) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    out[c] = v[1] * A[6 + c] - v[2] * A[3 + c];
-    out[3 + c] = v[2] * A[c] - v[0] * A[6 + c];
-    out[6 + c] = v[0] * A[3 + c] - v[1] * A[c];
-  }
-}
-
 __device__ __forceinline__ void tangent_basis(const double* t, double* b1, double* b2) {
   const double a0 = fabs(t[0]), a1 = fabs(t[1]), a2 = fabs(t[2]);
   int j = a1 < a0 ? 1 : 0;
@@ -69,15 +59,15 @@ __device__ __forceinline__ void tangent_basis(const double* t, double* b1, doubl
 __device__ __forceinline__ void model_matrices(const double* R, const double* t, double (&M)[6][9]) {
   double b1[3], b2[3], tmp[9];
   tangent_basis(t, b1, b2);
-  skew_mul(t, R, M[0]);
+  skew_times(t, R, M[0]);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const double e[3] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0};
-    skew_mul(e, R, tmp);
-    skew_mul(t, tmp, M[1 + k]);
+    skew_times(e, R, tmp);
+    skew_times(t, tmp, M[1 + k]);
   }
-  skew_mul(b1, R, M[4]);
-  skew_mul(b2, R, M[5]);
+  skew_times(b1, R, M[4]);
+  skew_times(b2, R, M[5]);
 }
 
 // the calibrated match i of pair p, as calibrate_kernel computes it; ok: finite and allowed by mask_in
@@ -148,20 +138,11 @@ __device__ __forceinline__ void apply_step(const double* R, const double* t, con
   so3_exp_series(th2, A, B, So3Literals());
   // exp([w]x) R = R + A [w]x R + B [w]x [w]x R
   double KR[9], KKR[9], X[9];
-  skew_mul(w, R, KR);
-  skew_mul(w, KR, KKR);
+  skew_times(w, R, KR);
+  skew_times(w, KR, KKR);
 #pragma unroll
   for (int i = 0; i < 9; ++i) X[i] = R[i] + A * KR[i] + B * KKR[i];
-  const double i0 = 1.0 / sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Rc[i] = X[i] * i0;
-  const double d = Rc[0] * X[3] + Rc[1] * X[4] + Rc[2] * X[5];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Rc[3 + i] = X[3 + i] - d * Rc[i];
-  const double i1 = 1.0 / sqrt(Rc[3] * Rc[3] + Rc[4] * Rc[4] + Rc[5] * Rc[5]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) Rc[3 + i] *= i1;
-  cross3(Rc, Rc + 3, Rc + 6);
+  orthonormalise_rows(X, Rc);
   double b1[3], b2[3];
   tangent_basis(t, b1, b2);
 #pragma unroll

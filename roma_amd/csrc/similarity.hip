@@ -672,8 +672,6 @@ long layout_sim(int P, int N, int iters, long* off) {
   return ws_layout(SIM_S, SIM_R, P, N, iters, extra, 3, off);
 }
 
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 int check_args_sim(const char* fn, const void* X, const void* Y, const void* ws, int P, int N, int iters, float threshold, int scoring,
                    long ws_bytes) {
   ROMA_REQUIRE(X && Y && ws, ROMA_E_ARG, "%s: null pointer", fn);

@@ -17,12 +17,11 @@
 //   scatter   x / visible per node, track_of_match per match
 // Integer atomics only (max, or, compare-and-swap), all of them set operations: no result depends on the order of arrival.
 #include <algorithm>
-#include "common.h"
+#include "multiview.h"
 
 namespace roma {
 namespace {
 
-constexpr int MAX_VIEWS = 32;
 constexpr int THREADS = 256;
 constexpr int SCAN_THREADS = 1024;
 constexpr unsigned UNION_RETRY_CAP = 1u << 20;      // a guard against a mistake hanging the device, not a path correct code takes
@@ -191,6 +190,7 @@ __global__ void __launch_bounds__(THREADS) tracks_count_kernel(Workspace ws, int
   }
 }
 
+// (the loop of depth_fuse.hip's fuse_scan_kernel, written out in both: profiles/multiview_shared_code_micro.txt)
 // one workgroup: block_counts[b][0] becomes the number of qualifying roots in the blocks before b; counts[0..2] the totals
 __global__ void __launch_bounds__(SCAN_THREADS) tracks_scan_kernel(Workspace ws, int blocks, int* counts) {
   __shared__ unsigned s_wave[SCAN_THREADS / 64];
@@ -344,9 +344,7 @@ extern "C" int roma_build_tracks(const float* matches, const float* certainty, c
   ROMA_REQUIRE(workspace_size >= workspace_bytes(C), ROMA_E_SHAPE, "roma_build_tracks: workspace of %ld bytes, roma_tracks_workspace asks for %ld",
                workspace_size, workspace_bytes(C));
   ROMA_REQUIRE(aligned16(matches) && aligned16(workspace), ROMA_E_ALIGN, "roma_build_tracks: matches and workspace must be 16-byte aligned");
-  ROMA_REQUIRE((reinterpret_cast<uintptr_t>(x) & 7) == 0 && (reinterpret_cast<uintptr_t>(certainty) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(pairs) & 3) == 0 && (reinterpret_cast<uintptr_t>(views) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(track_of_match) & 3) == 0 && (reinterpret_cast<uintptr_t>(counts) & 3) == 0,
+  ROMA_REQUIRE(aligned8(x) && aligned4(certainty) && aligned4(pairs) && aligned4(views) && aligned4(track_of_match) && aligned4(counts),
                ROMA_E_ALIGN, "roma_build_tracks: a pointer is not aligned to its element");
 
   const long mk = (long)M * k, vt = (long)V * T;

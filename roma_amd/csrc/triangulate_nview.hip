@@ -5,7 +5,7 @@
 // Convention (find_absolute_pose): x_v ~ K_v (R_v X + t_v), v = 0 .. V-1.  There is no batch of reconstructions: the views are the
 // batch.  The observations are read in place: view v's point n = r * row_len + c is the float2 at obs[v] + r * row_stride +
 // c * point_stride (floats), so V warps in V tensors need no copy; the V base pointers, the optional per-view map to pixels and the
-// optional per-view visibility pointers are kernel arguments by value (ViewTable).
+// optional per-view visibility pointers are kernel arguments by value (multiview.h's ObsTable).
 //
 // One launch, grid (blocks of THREADS columns, rows): a 2-D grid, no integer division per point.
 //   Per block, threads 0 .. V-1 in fp64: K_v^-1 (invert_k), the centre C_v = -R_v^T t_v; then c0 = the mean of the centres of the
@@ -32,19 +32,12 @@
 //   A point with fewer than two views in its set, or without a finite solution, gets exact zeros everywhere (views = 0); any other
 //   point its values, valid or not; no NaN or inf is ever written.  No atomics, no workspace; tests/triangulate_nview_ref.py restates
 //   it in numpy.
-#include "twoview_math.h"
+#include "multiview.h"
 
 namespace roma {
 namespace {
 
-constexpr int THREADS = 256, MAX_VIEWS = 32;
-
-// kernel arguments by value: base pointers, visibility pointers (null = always visible), pixel = s * c + o per coordinate
-struct ViewTable {
-  const float* obs[MAX_VIEWS];
-  const unsigned char* vis[MAX_VIEWS];
-  float px[MAX_VIEWS][4];          // sx, ox, sy, oy
-};
+constexpr int THREADS = 256;
 
 // fp32 per-view constants, in LDS
 struct ViewConst {
@@ -133,7 +126,7 @@ __device__ __forceinline__ Normal evaluate(const ViewConst* vc, const float2* co
   return n;
 }
 
-__global__ __launch_bounds__(THREADS) void triangulate_nview_kernel(ViewTable tab, NviewParams prm, const double* __restrict__ K,
+__global__ __launch_bounds__(THREADS) void triangulate_nview_kernel(ObsTable tab, NviewParams prm, const double* __restrict__ K,
                                                                     const double* __restrict__ R, const double* __restrict__ t,
                                                                     float* __restrict__ points, float* __restrict__ depth,
                                                                     float* __restrict__ reproj_out, float* __restrict__ cos_out,
@@ -362,16 +355,8 @@ extern "C" int roma_triangulate_nview(const float* const* obs, const float* to_p
                "roma_triangulate_nview: max_view_error, max_reproj and max_cos_parallax must not be NaN");
   ROMA_REQUIRE(max_view_error > 0.f, ROMA_E_ARG, "roma_triangulate_nview: max_view_error must be positive (+inf = every observed view), got %g",
                (double)max_view_error);
-  ViewTable tab;
-  for (int v = 0; v < MAX_VIEWS; ++v) {
-    const int u = v < V ? v : 0;
-    ROMA_REQUIRE(obs[u] != nullptr, ROMA_E_ARG, "roma_triangulate_nview: null pointer (observations of view %d)", u);
-    ROMA_REQUIRE((reinterpret_cast<uintptr_t>(obs[u]) & 7) == 0, ROMA_E_ALIGN,
-                 "roma_triangulate_nview: the observations of view %d must be 8-byte aligned", u);
-    tab.obs[v] = obs[u];
-    tab.vis[v] = visible ? visible[u] : nullptr;
-    for (int i = 0; i < 4; ++i) tab.px[v][i] = to_px ? to_px[4 * u + i] : ((i & 1) ? 0.f : 1.f);
-  }
+  ObsTable tab;
+  if (int rc = fill_obs_table("roma_triangulate_nview", obs, to_px, visible, V, tab)) return rc;
   NviewParams prm;
   prm.V = V; prm.row_len = row_len; prm.iters = iters; prm.min_views = min_views; prm.ref_view = ref_view;
   prm.robust = max_view_error < __builtin_inff() ? 1 : 0;

@@ -1,6 +1,9 @@
 // The fp64 device helpers of the two-view geometry kernels (geometry.hip, essential.hip, pose_refine.hip, fundamental_refine.hip,
-// homography_refine.hip): small 3 x 3 algebra, the unrolled elimination, the LDS Jacobi, the Sampson residual written out in fused
-// multiply-adds, the series of exp([w]x), the de-normalisation (select_kernel, the F refinement), and what the refinement kernels run
+// homography_refine.hip, triangulate.hip; absolute_pose.hip and similarity.hip through ransac_common.h) and, through multiview.h, of
+// the multi-view kernels (triangulate_nview.hip, tracks.hip, bundle.hip, depth_fuse.hip, motion_average.hip): small 3 x 3 algebra,
+// the skew product, the Gram-Schmidt on a rotation's rows, the unrolled elimination, the LDS Jacobi, the Sampson residual written out
+// in fused multiply-adds, the series of exp([w]x), the de-normalisation (select_kernel, the F
+// refinement), and what the refinement kernels run
 // alike: the fixed-order block reduction, the damped Cholesky step, (F and H) the Hartley normalisation over the usable matches and
 // (host) the checks of their entry points.  No __global__ code and no
 // device data: what the RANSAC scoring needs beyond this is ransac_common.h.  DESIGN.md §3.4.
@@ -41,6 +44,30 @@ __device__ __forceinline__ void cross3(const double* a, const double* b, double*
   c[0] = a[1] * b[2] - a[2] * b[1];
   c[1] = a[2] * b[0] - a[0] * b[2];
   c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// out = [v]x A (3 x 3, row major)
+__device__ __forceinline__ void skew_times(const double* v, const double* A, double* out) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    out[c] = v[1] * A[6 + c] - v[2] * A[3 + c];
+    out[3 + c] = v[2] * A[c] - v[0] * A[6 + c];
+    out[6 + c] = v[0] * A[3 + c] - v[1] * A[c];
+  }
+}
+
+// Gram-Schmidt on the rows of X into Rc: r0, r1 made orthogonal to r0, r2 = r0 x r1
+__device__ __forceinline__ void orthonormalise_rows(const double* X, double* Rc) {
+  const double i0 = 1.0 / sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Rc[i] = X[i] * i0;
+  const double d = Rc[0] * X[3] + Rc[1] * X[4] + Rc[2] * X[5];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Rc[3 + i] = X[3 + i] - d * Rc[i];
+  const double i1 = 1.0 / sqrt(Rc[3] * Rc[3] + Rc[4] * Rc[4] + Rc[5] * Rc[5]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) Rc[3 + i] *= i1;
+  cross3(Rc, Rc + 3, Rc + 6);
 }
 
 // ------------------------------------------------------------------------------------------------ Hartley normalisation record

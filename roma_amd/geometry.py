@@ -167,15 +167,20 @@ def _args(threshold, max_iters, lo_iters):
         raise ValueError(f"lo_iters must be >= 0, got {lo_iters}")
 
 
+def _workspace_layout(entry, regions, *shape):
+    """(total bytes, [region offsets]) from the library's `entry`(*shape, offsets); raises ValueError on a shape it refuses"""
+    off = (ctypes.c_long * regions)()
+    total = getattr(_lib.load(), entry)(*shape, ctypes.cast(off, ctypes.c_void_p))
+    if total < 0:
+        check(int(total), entry)
+    return int(total), list(off)
+
+
 def workspace_layout(kind, P, N, iters):
     """(total bytes, [region offsets]) of the workspace (include/roma_hip.h: the 9 regions of roma_ransac_workspace, the 10 of
     roma_essential_workspace for KIND_E)."""
     workspace, _, _, regions, calibrated = _ENTRIES[kind]
-    off = (ctypes.c_long * regions)()
-    total = getattr(_lib.load(), workspace)(*(() if calibrated else (kind,)), P, N, iters, ctypes.cast(off, ctypes.c_void_p))
-    if total < 0:
-        check(int(total), workspace)
-    return int(total), list(off)
+    return _workspace_layout(workspace, regions, *(() if calibrated else (kind,)), P, N, iters)
 
 
 def _chunks(kind, P, N, iters):
@@ -823,7 +828,7 @@ def _popcount(views):
 
 
 def _triangulate_nview(obs, to_px, vis, vis_stride, K, R, t, rows, row_len, row_stride, point_stride, gates, device, keep):
-    """roma_triangulate_nview on V observation pointers (ints) and optional visibility pointers (ints or None); `keep` holds the tensors
+    """roma_triangulate_nview on V observation pointers and optional visibility pointers (sequences of ints, or None); `keep` holds the tensors
     behind them.  -> points (N,3), depth, reproj, cos_parallax fp32, views int32, valid bool, N = rows * row_len"""
     V = len(obs)
     view_error, iters, min_views, max_reproj, max_cos, ref_view = gates
@@ -861,6 +866,33 @@ def _poses(R, t, V, device):
     return R.to(torch.float64).contiguous(), t.to(torch.float64).contiguous()
 
 
+def _threshold_px(threshold):
+    thr = float(threshold)
+    if not 0.0 < thr < 1e18:
+        raise ValueError(f"threshold must be positive pixels, got {threshold}")
+    return thr
+
+
+def _observations(x, visible, min_views):
+    """x (V,N,2), any float dtype, and visible (V,N) or None, as triangulate_nview, bundle_adjust and global_positions take them ->
+    (xs fp32 contiguous, vis uint8 contiguous or None, V, N, the ctypes table of the V observation pointers, that of the V visibility
+    pointers or None); the tables point into xs and vis, which the caller keeps alive until the launch is queued"""
+    if x.dim() != 3 or x.shape[-1] != 2 or not x.is_floating_point():
+        raise ValueError(f"expected floating-point observations (V,N,2), got {tuple(x.shape)} {x.dtype}")
+    V, N = x.shape[0], x.shape[1]
+    if not min_views <= V <= _MAX_VIEWS:
+        raise ValueError(f"{V} views: {min_views} to {_MAX_VIEWS} are supported")
+    if N < 1:
+        raise ValueError("no points")
+    if visible is not None and visible.shape != (V, N):
+        raise ValueError(f"visible {tuple(visible.shape)} does not match the observations {tuple(x.shape)}")
+    xs = x.to(torch.float32).contiguous()
+    vis = None if visible is None else visible.to(torch.uint8).contiguous()
+    obs_tab = (ctypes.c_void_p * V)(*[xs.data_ptr() + 8 * N * v for v in range(V)])
+    vis_tab = None if vis is None else (ctypes.c_void_p * V)(*[vis.data_ptr() + N * v for v in range(V)])
+    return xs, vis, V, N, obs_tab, vis_tab
+
+
 def triangulate_nview(x, R, t, K, *, visible=None, max_view_error=None, iters=3, min_views=2, max_reproj_error=None, min_parallax_deg=0.0,
                       ref_view=0):
     """3-D points of tracks seen in V posed views (2 <= V <= 32), each triangulated from all the views that see it, with the views that
@@ -886,20 +918,10 @@ def triangulate_nview(x, R, t, K, *, visible=None, max_view_error=None, iters=3,
     be captured in a hipGraph."""
     gates = _nview_gates(max_view_error, iters, min_views, max_reproj_error, min_parallax_deg, ref_view)
     _need_gpu(x, visible)
-    if x.dim() != 3 or x.shape[-1] != 2 or not x.is_floating_point():
-        raise ValueError(f"expected floating-point observations (V,N,2), got {tuple(x.shape)} {x.dtype}")
-    V, N = x.shape[0], x.shape[1]
-    if N < 1:
-        raise ValueError("no points")
-    if visible is not None and visible.shape != (V, N):
-        raise ValueError(f"visible {tuple(visible.shape)} does not match the observations {tuple(x.shape)}")
-    xs = x.to(torch.float32).contiguous()
-    vis = None if visible is None else visible.to(torch.uint8).contiguous()
+    xs, vis, V, N, obs_tab, vis_tab = _observations(x, visible, 2)
     Rp, tp = _poses(R, t, V, x.device)
     Kp = _intrinsics(K, V, x.device, "K")
-    obs = [xs.data_ptr() + 8 * N * v for v in range(V)]
-    vp = None if vis is None else [vis.data_ptr() + N * v for v in range(V)]
-    points, depth, reproj, cosp, views, valid = _triangulate_nview(obs, None, vp, N, Kp, Rp, tp, 1, N, 0, 2, gates, x.device, (xs, vis))
+    points, depth, reproj, cosp, views, valid = _triangulate_nview(obs_tab, None, vis_tab, N, Kp, Rp, tp, 1, N, 0, 2, gates, x.device, (xs, vis))
     return MultiViewTriangulation(points, depth, reproj, cosp, views, _popcount(views), valid)
 
 
@@ -1271,11 +1293,7 @@ def _points3d(X, x):
 
 def absolute_pose_workspace_layout(P, N, iters):
     """(total bytes, [region offsets]) of the workspace of roma_absolute_pose_hypotheses (include/roma_hip.h: 12 regions)"""
-    off = (ctypes.c_long * _AP_REGIONS)()
-    total = _lib.load().roma_absolute_pose_workspace(P, N, iters, ctypes.cast(off, ctypes.c_void_p))
-    if total < 0:
-        check(int(total), "roma_absolute_pose_workspace")
-    return int(total), list(off)
+    return _workspace_layout("roma_absolute_pose_workspace", _AP_REGIONS, P, N, iters)
 
 
 def _ap_chunks(P, N, iters):
@@ -1513,11 +1531,7 @@ def _clouds(X, Y):
 
 def similarity_workspace_layout(P, N, iters):
     """(total bytes, [region offsets]) of the workspace of roma_similarity_hypotheses (include/roma_hip.h: 12 regions)"""
-    off = (ctypes.c_long * _SIM_REGIONS)()
-    total = _lib.load().roma_similarity_workspace(P, N, iters, ctypes.cast(off, ctypes.c_void_p))
-    if total < 0:
-        check(int(total), "roma_similarity_workspace")
-    return int(total), list(off)
+    return _workspace_layout("roma_similarity_workspace", _SIM_REGIONS, P, N, iters)
 
 
 def _sim_chunks(P, N, iters):
@@ -1730,11 +1744,7 @@ class BundleResult:
 
 def bundle_workspace_layout(V, N):
     """-> (bytes, offsets of the 11 regions) of roma_bundle_workspace; raises ValueError on a bad shape"""
-    off = (ctypes.c_long * _BUNDLE_REGIONS)()
-    need = _lib.load().roma_bundle_workspace(int(V), int(N), ctypes.cast(off, ctypes.c_void_p))
-    if need < 0:
-        check(int(need), "roma_bundle_workspace")
-    return int(need), list(off)
+    return _workspace_layout("roma_bundle_workspace", _BUNDLE_REGIONS, int(V), int(N))
 
 
 def _fixed_mask(fixed, V):
@@ -1775,27 +1785,15 @@ def bundle_adjust(x, R, t, K, X, *, visible=None, threshold=2.0, iters=10, fixed
     status word.  fp64 relative to the mean camera centre: the result does not depend on where the world's origin is.  Sums are taken
     in a fixed order (no floating-point atomics): bitwise reproducible.  The decision to keep a step is taken on the device: no host
     synchronisation, the call can be captured in a hipGraph."""
-    thr, iters = float(threshold), int(iters)
-    if not 0.0 < thr < 1e18:
-        raise ValueError(f"threshold must be positive pixels, got {threshold}")
+    thr, iters = _threshold_px(threshold), int(iters)
     if not 0 <= iters <= 50:
         raise ValueError(f"iters must be in [0, 50], got {iters}")
     _need_gpu(x, visible, X)
-    if x.dim() != 3 or x.shape[-1] != 2 or not x.is_floating_point():
-        raise ValueError(f"expected floating-point observations (V,N,2), got {tuple(x.shape)} {x.dtype}")
-    V, N = x.shape[0], x.shape[1]
-    if not 2 <= V <= _MAX_VIEWS:
-        raise ValueError(f"{V} views: 2 to {_MAX_VIEWS} are supported")
-    if N < 1:
-        raise ValueError("no points")
+    xs, vis, V, N, obs_tab, vis_tab = _observations(x, visible, 2)
     if X.shape != (N, 3) or not X.is_floating_point():
         raise ValueError(f"points {tuple(X.shape)} {X.dtype}: expected floating-point ({N},3)")
-    if visible is not None and visible.shape != (V, N):
-        raise ValueError(f"visible {tuple(visible.shape)} does not match the observations {tuple(x.shape)}")
     bits = _fixed_mask(fixed, V)
     dev = x.device
-    xs = x.to(torch.float32).contiguous()
-    vis = None if visible is None else visible.to(torch.uint8).contiguous()
     Rp, tp = _poses(R, t, V, dev)
     Kp = _intrinsics(K, V, dev, "K")
     Xp = X.to(torch.float64).contiguous()
@@ -1805,8 +1803,6 @@ def bundle_adjust(x, R, t, K, X, *, visible=None, threshold=2.0, iters=10, fixed
     Ro, to, Xo, cost = torch.empty((V, 3, 3), **f64), torch.empty((V, 3), **f64), torch.empty((N, 3), **f64), torch.empty((2,), **f64)
     mask = torch.empty((V, N), dtype=torch.uint8, device=dev)
     ints = torch.empty((3,), dtype=torch.int32, device=dev)                       # count, steps, status
-    obs_tab = (ctypes.c_void_p * V)(*[xs.data_ptr() + 8 * N * v for v in range(V)])
-    vis_tab = None if vis is None else (ctypes.c_void_p * V)(*[vis.data_ptr() + N * v for v in range(V)])
     check(_lib.load().roma_bundle_adjust(ctypes.cast(obs_tab, ctypes.c_void_p), None, None if vis_tab is None else ctypes.cast(vis_tab, ctypes.c_void_p),
                                          2, Kp.data_ptr(), Rp.data_ptr(), tp.data_ptr(), Xp.data_ptr(), V, N, bits, thr, iters, Ro.data_ptr(),
                                          to.data_ptr(), Xo.data_ptr(), mask.data_ptr(), cost.data_ptr(), ints.data_ptr(), ints.data_ptr() + 4,
@@ -1918,11 +1914,7 @@ def average_rotations(R_rel, pairs, V, *, weights=None, root=0, sigma_deg=5.0, i
 
 def positions_workspace_layout(V, N, M):
     """-> (bytes, offsets of the 11 regions) of roma_positions_workspace; raises ValueError on a bad shape"""
-    off = (ctypes.c_long * _POSITIONS_REGIONS)()
-    need = _lib.load().roma_positions_workspace(int(V), int(N), int(M), ctypes.cast(off, ctypes.c_void_p))
-    if need < 0:
-        check(int(need), "roma_positions_workspace")
-    return int(need), list(off)
+    return _workspace_layout("roma_positions_workspace", _POSITIONS_REGIONS, int(V), int(N), int(M))
 
 
 def global_positions(x, R, K, pairs, t_rel, *, visible=None, threshold=4.0, rounds=4, root=0):
@@ -1936,22 +1928,12 @@ def global_positions(x, R, K, pairs, t_rel, *, visible=None, threshold=4.0, roun
     direction of t_rel is used (X_b = R_rel X_a + t_rel); threshold in pixels; root: the view at the origin.  The scale is fixed by
     sum |C_v|^2 = 1.  Returns a GlobalPositions.  Sums in a fixed order, no floating-point atomics: bitwise reproducible; no host
     synchronisation: the call can be captured in a graph."""
-    thr, rounds = float(threshold), int(rounds)
-    if not 0.0 < thr < 1e18:
-        raise ValueError(f"threshold must be positive pixels, got {threshold}")
+    thr, rounds = _threshold_px(threshold), int(rounds)
     if not 2 <= rounds <= 8:
         raise ValueError(f"rounds must be in [2, 8], got {rounds}")
     _need_gpu(x, visible)
-    if x.dim() != 3 or x.shape[-1] != 2 or not x.is_floating_point():
-        raise ValueError(f"expected floating-point observations (V,N,2), got {tuple(x.shape)} {x.dtype}")
-    V, N = x.shape[0], x.shape[1]
-    if not 3 <= V <= _MAX_VIEWS:
-        raise ValueError(f"{V} views: 3 to {_MAX_VIEWS} are supported")
-    if N < 1:
-        raise ValueError("no points")
+    xs, vis, V, N, obs_tab, vis_tab = _observations(x, visible, 3)
     root = _view_index(root, V)
-    if visible is not None and visible.shape != (V, N):
-        raise ValueError(f"visible {tuple(visible.shape)} does not match the observations {tuple(x.shape)}")
     dev = x.device
     if not torch.is_tensor(t_rel):
         t_rel = torch.as_tensor(t_rel, dtype=torch.float64).to(dev)
@@ -1963,8 +1945,6 @@ def global_positions(x, R, K, pairs, t_rel, *, visible=None, threshold=4.0, roun
         raise ValueError(f"{M} edges: 1 to {_MAX_EDGES} are supported")
     pr = _edges(pairs, M, dev)
     tr = t_rel.to(torch.float64).contiguous()
-    xs = x.to(torch.float32).contiguous()
-    vis = None if visible is None else visible.to(torch.uint8).contiguous()
     Rp, _ = _poses(R, torch.zeros((V, 3), dtype=torch.float64, device=dev), V, dev)
     Kp = _intrinsics(K, V, dev, "K")
     need, _ = positions_workspace_layout(V, N, M)
@@ -1973,8 +1953,6 @@ def global_positions(x, R, K, pairs, t_rel, *, visible=None, threshold=4.0, roun
     t, centres, points, lam = torch.empty((V, 3), **f64), torch.empty((V, 3), **f64), torch.empty((N, 3), **f64), torch.empty((2,), **f64)
     mask = torch.empty((V, N), dtype=torch.uint8, device=dev)
     ints = torch.empty((2,), dtype=torch.int32, device=dev)                       # count, status
-    obs_tab = (ctypes.c_void_p * V)(*[xs.data_ptr() + 8 * N * v for v in range(V)])
-    vis_tab = None if vis is None else (ctypes.c_void_p * V)(*[vis.data_ptr() + N * v for v in range(V)])
     check(_lib.load().roma_global_positions(ctypes.cast(obs_tab, ctypes.c_void_p), None, None if vis_tab is None else ctypes.cast(vis_tab, ctypes.c_void_p),
                                             2, Kp.data_ptr(), Rp.data_ptr(), pr.data_ptr(), tr.data_ptr(), V, N, M, root, thr, rounds, t.data_ptr(),
                                             centres.data_ptr(), points.data_ptr(), mask.data_ptr(), ints.data_ptr(), lam.data_ptr(),

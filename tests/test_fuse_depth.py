@@ -268,6 +268,23 @@ def test_block_edges(shape):
 
 
 @pytest.mark.gpu
+def test_blocks_beyond_the_first_pass_of_the_scan():
+    """Two maps of 740 x 730: 528 blocks each, 1056 in all, 32 more than the scan kernel's 1024 threads take in one pass, so the ranks
+    of the pixels that view 1 emits from its last 45 rows need the carry of the first pass.  At 1.5 million decisions the scene cannot
+    keep DS.MARGIN; every decision lies 1e-9 or more from its threshold, four orders above the fp64 rounding of the device's and the
+    restatement's expressions (below 1e-13 of quantities of order 1), so the restatement decides each one as the device does."""
+    shape = (740, 730)
+    sc = DS.fuse_scene(2, 1, shapes=(shape,), check=False)
+    assert all(len(m) == 0 or m.min() >= 1e-9 for m in sc["ref"]["margins"].values())
+    per_view = -(-shape[0] * shape[1] // PIXELS_PER_BLOCK)
+    assert 2 * per_view == 1056
+    got = _check_scene(sc)
+    k = int(got["counts"][0])
+    block = got["view"][:k].astype(np.int64) * per_view + got["pixel"][:k] // PIXELS_PER_BLOCK
+    assert (np.diff(block) >= 0).all() and (block >= 1024).sum() > 1000 and (block < 1024).sum() > 1000
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("delta", [-300, -1, 0, 1])
 def test_max_points_below_equal_and_above(delta):
     sc = DS.fuse_scene(3, 0)

@@ -382,6 +382,37 @@ def test_unusable_matches_change_nothing_else():
     _assert_equal(got, base)
 
 
+@functools.lru_cache(maxsize=None)
+def second_pass_inputs():
+    """One pair, 300 matches.  View 0 is 1040 x 1024 at cell = 2: 266240 cells, 1040 blocks of 256, 16 more than the scan kernel's 1024
+    threads take in one pass; a track's root is its cell in view 0 (the lowest id of the component), and 100 of the A ends lie in the
+    last 16 pixel rows, which are the cells of blocks 1024 to 1039.  The B ends lie in distinct cells of a 64 x 64 view."""
+    k, cell, sizes = 300, 2, ((1040, 1024), (64, 64))
+    rng = np.random.default_rng(11)
+    xa, ya = rng.uniform(0, 1024, k), np.concatenate([rng.uniform(0, 1024, 200), rng.uniform(1024, 1040, 100)])
+    cb = rng.permutation(32 * 32)[:k]
+    xb, yb = (cb % 32 + rng.uniform(0.1, 0.9, k)) * cell, (cb // 32 + rng.uniform(0.1, 0.9, k)) * cell
+    matches = np.stack([norm_px(xa, 1024), norm_px(ya, 1040), norm_px(xb, 64), norm_px(yb, 64)], -1)[None]
+    certainty = rng.uniform(0.1, 1.0, (1, k)).astype(np.float32)
+    return _frozen(matches=matches, certainty=certainty, pairs=np.array([(0, 1)], np.int32), sizes=sizes), cell
+
+
+@pytest.mark.gpu
+def test_roots_beyond_the_first_pass_of_the_scan():
+    """The scan of the per-block counts takes the blocks in passes of 1024: the ranks of the roots in blocks 1024 and above need the
+    carry of the first pass."""
+    inp, cell = second_pass_inputs()
+    want = TR.build_tracks_ref(**inp, cell=cell, max_tracks=T_FULL)
+    got = _run(**inp, cell=cell)
+    _assert_equal(got, want)
+    kept = int(got["counts"][0])
+    assert 250 < kept <= 300
+    # the rows ascend with the root's cell id: the last ones are the tracks of the last 16 pixel rows of view 0
+    cells = (np.floor(got["x"][0, :kept, 1] / cell) * 512 + np.floor(got["x"][0, :kept, 0] / cell)).astype(np.int64)
+    assert got["visible"][0, :kept].all() and (np.diff(cells) > 0).all()
+    assert 80 < (cells >= 1024 * 256).sum() < kept - 80
+
+
 @pytest.mark.gpu
 def test_truncation_keeps_the_first_rows():
     full, want = scene_ref(5, 0), scene_ref(5, 0, 100)
