@@ -785,6 +785,36 @@ int roma_depth_fuse(const float* const* depths, const int* dims, const double* K
                     int* views, unsigned char* num_views, float* points, unsigned char* view, int* pixel, int* point_views, int* counts,
                     void* workspace, long workspace_size, void* stream);
 
+/* Point-cloud rendering (csrc/render_points.hip): N points drawn into the depth maps of V posed views (1 <= V <= 32) by
+ * a z-buffered splat, and per point the views that see it.  Convention of roma_depth_fuse: x_v ~ K_v (R_v X + t_v); pixel (row i,
+ * column j) covers [j, j+1) x [i, i+1).  tests/render_points_ref.py restates the definition.
+ *   points: (N,3) fp32 device, 4-byte aligned, read in place, 1 <= N <= 2^31 - 1;  mask: (N) uint8 device or NULL.  A point is live
+ *     when its three coordinates are finite and mask is NULL or mask[n] != 0;
+ *   K, R: (V,3,3), t: (V,3) fp64 device.  A view is usable when K_v is upper triangular with fx fy k22 != 0 and K_v, R_v, t_v are
+ *     finite; an unusable view gets an empty map and its bit is never set;
+ *   H, W: the shape of every map, 1 to 32768 each, V H W <= 2^31 - 1;  radius: 0 to 4;  depth_tol: finite, >= 0.
+ * Projection of a live point into a usable view, fp64 with explicit fused multiply-adds: q = P_v (X, 1) with P_v = K_v [R_v | t_v];
+ * skip unless q.z > 0 and q is finite; (u, w) = q.xy (1 / q.z); skip unless 0 <= u < W and 0 <= w < H (tested in floating point before
+ * anything becomes an integer); z32 = (float) q.z, skip unless it is finite and > 0; (j, i) = (floor u, floor w).
+ * Splat: key = bits(z32) << 32 | n; every pixel (i + di, j + dj), |di|, |dj| <= radius, inside the map takes the unsigned 64-bit
+ * minimum of its word (all ones at first) and key: the winner is the nearest point and, on exactly equal z32, the lowest index,
+ * whatever order the points arrive in.
+ * Outputs, device, all required.  depth (V,H,W) fp32 = the winner's z32, index (V,H,W) int32 = its n; 0.0f and -1 where nothing was
+ * drawn.  visible (N) int32: bit v is set when the point projects inside the map of the usable view v and (double) z32 <= (double)
+ * depth[v, i, j] (1 + depth_tol) at its own pixel (i, j); num_views (N) uint8 = its popcount; both 0 for a point that is not live.
+ * counts (4) int32: projections inside a map, covered pixels, set visibility bits, points that are not live (each modulo 2^32).
+ * workspace: roma_render_points_workspace(V, H, W, out_bytes) bytes, 16-byte aligned, need not be initialised: the V H W 64-bit keys,
+ * rounded up to 256; the counters are `counts` itself, cleared by the first launch.  The function (host only) stores the size of
+ * that one region in out_bytes (may be NULL) and returns a negative code for a bad shape.
+ * Four launches on `stream`: clear, splat (grid (ceil(N / 1024), V), four points per thread), resolve, visible.  The only atomics are
+ * the 64-bit unsigned min and one integer add per block and count: both commute, so the result is bitwise the same from run to run
+ * and under any permutation of the points' arrival.  No block waits for another, no host synchronisation: the call can be captured
+ * in a graph. */
+long roma_render_points_workspace(int V, int H, int W, long* out_bytes);
+int roma_render_points(const float* points, const unsigned char* mask, long N, const double* K, const double* R, const double* t, int V,
+                       int H, int W, int radius, double depth_tol, float* depth, int* index, int* visible, unsigned char* num_views,
+                       int* counts, void* workspace, long workspace_bytes, void* stream);
+
 /* Ground-truth warp of key-points from two depth maps and a relative pose (csrc/depth_warp.hip): warp_kpts of the
  * reference (romatch/utils/utils.py:358-455; get_gt_warp is this on the pixel grid).  Convention: X_B = R X_A + t, T = [R | t].
  *   x: (P,N,·) fp32 device, 8-byte aligned, normalised key-points of image A in columns 0-1 of rows `x_stride` floats apart: 2 for

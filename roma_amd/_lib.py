@@ -140,11 +140,14 @@ SIGNATURES = {
     "roma_depth_fuse_workspace": [c_int, c_long, c_void_p],
     "roma_depth_fuse": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_int, c_int, c_void_p,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
+    "roma_render_points_workspace": [c_int, c_int, c_int, c_void_p],
+    "roma_render_points": [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p],
 }
 _RESTYPES = {"roma_last_error": c_char_p, "roma_ransac_workspace": c_long, "roma_essential_workspace": c_long,
              "roma_race_select_workspace": c_long, "roma_absolute_pose_workspace": c_long, "roma_similarity_workspace": c_long,
              "roma_tracks_workspace": c_long, "roma_bundle_workspace": c_long, "roma_depth_fuse_workspace": c_long,
-             "roma_positions_workspace": c_long}
+             "roma_positions_workspace": c_long, "roma_render_points_workspace": c_long}
 
 _lib = None
 

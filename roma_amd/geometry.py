@@ -78,9 +78,14 @@ re-weighted from a majority vote of the pairwise translation directions.
 are checked against one another by forward-backward reprojection in fp64, every pixel keeps the views that agree with it and the mean
 of their depths, each surface point is owned by the lowest view that sees it, and the owners are compacted in a fixed order into one
 cloud of a fixed shape.
+
+`render_points` looks at that cloud again from a camera (csrc/render_points.hip): a z-buffered point splat into the depth maps of V
+posed views by a 64-bit integer atomic minimum — the nearest point per pixel, whatever order the points arrive in — and per point the
+views that see it and those in which a nearer surface is in the way.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 
@@ -2112,6 +2117,116 @@ def fuse_depth_maps(depths, R, t, K, *, sizes=None, max_reproj_error=1.0, max_de
         return out
 
     return FusedDepth(per_view(depth), per_view(valid), per_view(views), per_view(num_views), points, view, pixel, point_views, counts)
+
+
+# --------------------------------------------------------------------------------------------------------- point-cloud rendering
+RenderedViews = collections.namedtuple("RenderedViews", ("depth", "index", "visible", "num_views", "counts", "attributes"))
+RenderedViews.__doc__ = """What render_points returns, device tensors.  depth (V,H,W) fp32, the camera-frame z of the nearest point drawn
+into the pixel, and index (V,H,W) int32, its row in the cloud (the lowest row among exactly equal depths); 0 and -1 where nothing was
+drawn.  visible (N) int32: (visible >> v) & 1 says that view v sees point n, num_views (N) uint8 its popcount.  counts (4) int32:
+projections inside a map, covered pixels, set visibility bits, points that are not live.  attributes: (V,H,W,C) or None."""
+
+
+def render_points_workspace(V, H, W):
+    """-> bytes of roma_render_points_workspace; raises ValueError on a bad shape"""
+    need = _lib.load().roma_render_points_workspace(int(V), int(H), int(W), None)
+    if need < 0:
+        check(int(need), "roma_render_points_workspace")
+    return int(need)
+
+
+def render_points(points, R, t, K, shape, *, sizes=None, radius=0, depth_tol=0.05, mask=None, attributes=None):
+    """A cloud drawn into the depth maps of V posed views (1 <= V <= 32) by a z-buffered point splat, and per point the views that see
+    it (csrc/render_points.hip) — what looks at the cloud of fuse_depth_maps again from a camera: a depth map of the dense model for
+    lift_keypoints and find_absolute_pose, for warp_kpts and dense_match_metrics, and occlusion-aware visibility of every point in every
+    view.  Convention of fuse_depth_maps: x_v ~ K_v (R_v X + t_v); pixel (row i, column j) covers [j, j+1) x [i, i+1).
+    points: (N,3) contiguous fp32 on the device, read in place; anything else is refused (make it .float().contiguous()).  R (V,3,3), t
+    (V,3), or one pose (3,3), (3,) for V = 1; K (3,3) shared or (V,3,3); shape = (H, W), the same for all views; sizes: V pairs (H_img,
+    W_img), the image size K_v refers to, default the maps' shape — K_v is scaled by diag(W / W_img, H / H_img, 1).  mask: (N) bool or
+    uint8, a row with 0 is not drawn; for a fused cloud pass `fused.pixel >= 0`, since the rows past counts[0] are zeros and would draw
+    the world's origin.  A row that is not finite is not drawn either.  A view whose K is singular or not upper triangular, or whose
+    pose is not finite, gets an empty map and sees nothing.
+    A point is drawn where it projects in front of the view and inside the map, into every pixel within `radius` (0 to 4) of its own in
+    rows and columns; a pixel keeps the nearest point, in fp32, and among exactly equal depths the lowest row — by a 64-bit integer
+    atomic minimum, so the maps do not depend on the order the points arrive in and two calls agree bit for bit.  A view sees a point
+    when the point's depth is at most (1 + depth_tol) times the depth drawn at its own pixel.  With radius 0 the holes between splats
+    let hidden points through; radius 1 closes them at the resolution the cloud was made at.
+    attributes: (N,C), any dtype -> (V,H,W,C) = attributes[index], 0 where nothing was drawn (a torch gather).  Returns a RenderedViews.
+    tests/render_points_ref.py restates it.  No host synchronisation: the call can be captured in a hipGraph."""
+    try:
+        H, W = (int(s) for s in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"shape: expected (H, W), got {shape!r}") from None
+    if not (1 <= H <= 32768 and 1 <= W <= 32768):
+        raise ValueError(f"shape: expected (H, W) with sides in [1, 32768], got {shape!r}")
+    try:
+        rad, tol = int(radius), float(depth_tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"radius: expected an int and depth_tol a float, got {radius!r} and {depth_tol!r}") from None
+    if rad != radius or not 0 <= rad <= 4:
+        raise ValueError(f"radius must be an int in [0, 4], got {radius}")
+    if not 0.0 <= tol < math.inf:
+        raise ValueError(f"depth_tol must be finite and not negative, got {depth_tol}")
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[1] != 3 or not 1 <= points.shape[0] < 1 << 31:
+        raise ValueError(f"points: expected a (N,3) tensor with 1 <= N < 2^31, got {tuple(getattr(points, 'shape', ()))}")
+    N = int(points.shape[0])
+    single = tuple(getattr(R, "shape", ())) == (3, 3)
+    V = 1 if single else (int(R.shape[0]) if len(getattr(R, "shape", ())) == 3 else 0)
+    if not 1 <= V <= _MAX_VIEWS:
+        raise ValueError(f"R: expected (V,3,3) with 1 <= V <= {_MAX_VIEWS} or one (3,3), got {tuple(getattr(R, 'shape', ()))}")
+    for name, v, shapes in (("R", R, ((3, 3),) if single else ((V, 3, 3),)), ("t", t, ((3,),) if single else ((V, 3),)),
+                            ("K", K, ((3, 3), (V, 3, 3)))):
+        if tuple(getattr(v, "shape", ())) not in shapes:
+            raise ValueError(f"{name}: expected {' or '.join(str(s) for s in shapes)}, got {tuple(getattr(v, 'shape', ()))}")
+    if V * H * W >= 1 << 31:
+        raise ValueError(f"{V} maps of {H}x{W} have {V * H * W} pixels in all, at most 2^31 - 1 are supported")
+    if sizes is None:
+        scale = [(1.0, 1.0)] * V
+    else:
+        try:
+            sizes = [(int(h), int(w)) for h, w in sizes]
+        except (TypeError, ValueError):
+            raise ValueError("sizes: expected V pairs (H_img, W_img) of ints") from None
+        if len(sizes) != V or any(h < 1 or w < 1 for h, w in sizes):
+            raise ValueError(f"sizes: expected {V} pairs (H_img, W_img) of positive ints, got {sizes}")
+        scale = [(W / wi, H / hi) for hi, wi in sizes]
+    if mask is not None and (not torch.is_tensor(mask) or tuple(mask.shape) != (N,) or mask.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError(f"mask: expected a ({N},) bool or uint8 tensor, got {tuple(getattr(mask, 'shape', ()))} {getattr(mask, 'dtype', None)}")
+    if attributes is not None and (not torch.is_tensor(attributes) or attributes.dim() != 2 or attributes.shape[0] != N):
+        raise ValueError(f"attributes: expected a ({N},C) tensor, got {tuple(getattr(attributes, 'shape', ()))}")
+    _need_gpu(points, mask, attributes)
+    dev = points.device
+    if points.dtype != torch.float32 or not points.is_contiguous() or points.data_ptr() % 4:
+        raise ValueError(f"points: {points.dtype} with strides {points.stride()} cannot be read in place (contiguous float32); pass "
+                         ".float().contiguous() points")
+    if single:
+        R, t = R[None], t[None]
+    Rp, tp = _poses(R, t, V, dev)
+    Kp = _intrinsics(K, V, dev, "K")
+    if any(sc != (1.0, 1.0) for sc in scale):
+        Kp = Kp.clone()                                       # _intrinsics may have handed back the caller's own tensor
+    for v, (sx, sy) in enumerate(scale):                      # Python scalars: kernel arguments, no copy from the host
+        if sx != 1.0:
+            Kp[v, 0] *= sx
+        if sy != 1.0:
+            Kp[v, 1] *= sy
+    mk = None if mask is None else mask.contiguous().view(torch.uint8)
+    need = render_points_workspace(V, H, W)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    index = torch.empty((V, H, W), dtype=torch.int32, device=dev)
+    visible = torch.empty((N,), dtype=torch.int32, device=dev)
+    num_views = torch.empty((N,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((4,), dtype=torch.int32, device=dev)
+    check(_lib.load().roma_render_points(points.data_ptr(), None if mk is None else mk.data_ptr(), N, Kp.data_ptr(), Rp.data_ptr(),
+                                         tp.data_ptr(), V, H, W, rad, tol, depth.data_ptr(), index.data_ptr(), visible.data_ptr(),
+                                         num_views.data_ptr(), counts.data_ptr(), ws.data_ptr(), need, _stream()),
+          "roma_render_points")
+    drawn = None
+    if attributes is not None:
+        drawn = attributes[index.clamp(min=0).to(torch.int64)]
+        drawn = torch.where((index >= 0)[..., None], drawn, torch.zeros((), dtype=drawn.dtype, device=dev))
+    return RenderedViews(depth, index, visible, num_views, counts, drawn)
 
 
 def reconstruction_error(R, t, X, R_gt, t_gt, X_gt):
