@@ -49,7 +49,6 @@ namespace roma {
 namespace {
 
 constexpr int AP_S = 3, AP_R = 4;
-constexpr uint32_t STAGE_AP = 5u;
 constexpr int AP_POLISH = 2;
 constexpr int P3P_THREADS = 128;
 constexpr int AP_THREADS = 256, AP_WAVES = AP_THREADS / 64;
@@ -287,23 +286,8 @@ __global__ __launch_bounds__(P3P_THREADS) void p3p_kernel(const double* __restri
   const size_t base = (size_t)p * N;
 
   int idx[AP_S];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < AP_S; ++k) {
-    const uint32_t ctr = (((uint32_t)(p0 + p) * (uint32_t)iters + (uint32_t)h) * 8u + (uint32_t)k);
-    int got = -1;
-    for (uint32_t att = 0; att < 16; ++att) {
-      const uint32_t hs = fmix32(stream + ctr * 0x9E3779B1u + att * 0x7FEB352Du);
-      const int i = (int)(((uint64_t)hs * (uint64_t)(uint32_t)N) >> 32);
-      const float v = pts[base + i].x;
-      bool good = v == v;
-#pragma unroll
-      for (int j = 0; j < k; ++j) good = good && idx[j] != i;
-      if (good) { got = i; break; }
-    }
-    idx[k] = got;
-    ok = ok && got >= 0;
-  }
+  bool ok;
+  draw_sample<AP_S>(stream, (uint32_t)(p0 + p), iters, h, N, [&](int i) { const float v = pts[base + i].x; return v == v; }, idx, ok);
 #pragma unroll
   for (int k = 0; k < AP_S; ++k) samples[(size_t)t * AP_S + k] = ok ? idx[k] : -1;
   double* out_R = models + (size_t)t * AP_R * 9;
@@ -555,33 +539,13 @@ __global__ __launch_bounds__(256) void ap_score_kernel(const float4* __restrict_
   slab_cnt[o] = cnt;
 }
 
-// Cost (fp32 errors, fp64 sum in a fixed tree) and inlier count of (R, t') over the pair's N records: block_score of ransac_common.h
+// Cost and inlier count of (R, t') over the pair's N records: block_cost of ransac_common.h
 template <int SCORE>
 __device__ void ap_block_score(const double* R, const double* t, const Cam& cam, const float4* pq, const float* pvq, int N, float t2,
                                double* dred, int* ired, double& cost, int& cnt) {
-  const int tid = threadIdx.x;
   float m[12];
   compose_projection(R, t, cam, m);
-  double c = 0.0;
-  int n = 0;
-  for (int i = tid; i < N; i += 256) {
-    const float e = ap_point_error(m, pq[i], pvq[i]);
-    const bool in = e < t2;
-    n += in ? 1 : 0;
-    if constexpr (SCORE == SCORE_MSAC) c += (double)(in ? e : t2);
-    else c += (double)(in ? magsac_lookup(magsac_loss_cells, e, (float)MAGSAC_CELLS / t2) : 1.f);
-  }
-  if constexpr (SCORE == SCORE_MAGSAC) c *= (double)t2;
-  dred[tid] = c;
-  ired[tid] = n;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) { dred[tid] += dred[tid + o]; ired[tid] += ired[tid + o]; }
-    __syncthreads();
-  }
-  cost = dred[0];
-  cnt = ired[0];
-  __syncthreads();
+  block_cost<SCORE>(N, t2, [&](int i) { return ap_point_error(m, pq[i], pvq[i]); }, dred, ired, cost, cnt);
 }
 
 // ------------------------------------------------------------------------------------------ selection + local optimisation
@@ -819,12 +783,8 @@ long layout_ap(int P, int N, int iters, long* off) {
 int check_args_ap(const char* fn, const void* X, const void* x, const void* K, const void* ws, int P, int N, int iters, float threshold,
                   long ws_bytes) {
   ROMA_REQUIRE(X && x && K && ws, ROMA_E_ARG, "%s: null pointer", fn);
-  const int rc = check_shape(fn, P, N, iters, AP_S);
-  if (rc) return rc;
-  ROMA_REQUIRE(((long)P * iters + P3P_THREADS - 1) / P3P_THREADS <= 0x7FFFFFFFL, ROMA_E_SHAPE, "%s: P * iters = %ld samples in one call",
-               fn, (long)P * iters);
-  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
-  return check_workspace(fn, ws_bytes, layout_ap(P, N, iters, nullptr));
+  const int rc = check_problem(fn, P, N, iters, AP_S, P3P_THREADS, threshold);
+  return rc ? rc : check_workspace(fn, ws_bytes, layout_ap(P, N, iters, nullptr));
 }
 
 }  // namespace
@@ -847,38 +807,24 @@ extern "C" int roma_absolute_pose_hypotheses(const double* X, const double* x, c
   if (rc) return rc;
   rc = check_scoring(fn, scoring);
   if (rc) return rc;
-  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "%s: negative pair offset %d", fn, p0);
+  rc = check_pair_offset(fn, p0);
+  if (rc) return rc;
   long off[WA_N];
   layout_ap(P, N, iters, off);
-  char* w = static_cast<char*>(ws);
-  double* norm = (double*)(w + off[WS_NORM]);
-  float4* pts = (float4*)(w + off[WS_PTS]);
-  int* samples = (int*)(w + off[WS_SAMPLES]);
-  double* models = (double*)(w + off[WS_MODELS]);
-  int* valid = (int*)(w + off[WS_VALID]);
-  float* slab_cost = (float*)(w + off[WS_SLAB_COST]);
-  int* slab_cnt = (int*)(w + off[WS_SLAB_CNT]);
-  double* cost = (double*)(w + off[WS_COST]);
-  int* count = (int*)(w + off[WS_COUNT]);
-  double* tvec = (double*)(w + off[WA_TVEC]);
-  float* pv = (float*)(w + off[WA_PV]);
-  double* xn = (double*)(w + off[WA_XN]);
+  const Regions r = regions(ws, off);
+  double* tvec = region<double>(ws, off, WA_TVEC);
+  float* pv = region<float>(ws, off, WA_PV);
+  double* xn = region<double>(ws, off, WA_XN);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int M = iters * AP_R, C = (N + CHUNK - 1) / CHUNK;
-  const uint32_t sstream = fmix32((uint32_t)seed ^ (STAGE_AP * 0x9E3779B9u));
+  const uint32_t sstream = sample_stream(seed, STAGE_AP);
   const float t2 = threshold * threshold;
-  const long nt = (long)P * iters;
-  const dim3 gm((unsigned)((nt + P3P_THREADS - 1) / P3P_THREADS)), gs((unsigned)((M + 255) / 256), (unsigned)C, (unsigned)P);
-  const dim3 gr((unsigned)(((long)P * M + 255) / 256));
-  hipLaunchKernelGGL(ap_prepare_kernel, dim3(P), dim3(256), 0, st, X, x, K, N, norm, pts, pv, xn);
-  hipLaunchKernelGGL(p3p_kernel, gm, dim3(P3P_THREADS), 0, st, (const double*)xn, (const float4*)pts, P, N, iters, sstream, p0, samples,
-                     models, tvec, valid);
-  auto score = ap_score_kernel<SCORE_MSAC>;
-  if (scoring == SCORE_MAGSAC) score = ap_score_kernel<SCORE_MAGSAC>;
-  hipLaunchKernelGGL(score, gs, dim3(256), 0, st, (const float4*)pts, (const float*)pv, K, (const double*)models, (const double*)tvec,
-                     (const int*)valid, N, M, t2, slab_cost, slab_cnt);
-  hipLaunchKernelGGL(reduce_kernel, gr, dim3(256), 0, st, (const float*)slab_cost, (const int*)slab_cnt, (const int*)valid, P, M, C,
-                     cost, count);
+  const Grids g = ransac_grids(P, N, iters, AP_R, P3P_THREADS);
+  hipLaunchKernelGGL(ap_prepare_kernel, dim3(P), dim3(256), 0, st, X, x, K, N, r.norm, r.pts, pv, xn);
+  hipLaunchKernelGGL(p3p_kernel, g.solve, dim3(P3P_THREADS), 0, st, xn, r.pts, P, N, iters, sstream, p0, r.samples, r.models, tvec, r.valid);
+  const auto score = by_scoring(scoring, ap_score_kernel<SCORE_MSAC>, ap_score_kernel<SCORE_MAGSAC>);
+  hipLaunchKernelGGL(score, g.score, dim3(256), 0, st, r.pts, pv, K, r.models, tvec, r.valid, N, M, t2, r.slab_cost, r.slab_cnt);
+  hipLaunchKernelGGL(reduce_kernel, g.reduce, dim3(256), 0, st, r.slab_cost, r.slab_cnt, r.valid, P, M, C, r.cost, r.count);
   return check_launch(fn);
 }
 
@@ -891,17 +837,16 @@ extern "C" int roma_absolute_pose_select(const double* X, const double* x, const
   ROMA_REQUIRE(R && t && mask, ROMA_E_ARG, "%s: null pointer", fn);
   rc = check_scoring(fn, scoring);
   if (rc) return rc;
-  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "%s: negative lo_iters %d", fn, lo_iters);
+  rc = check_lo_iters(fn, lo_iters);
+  if (rc) return rc;
   ROMA_REQUIRE(aligned16(x), ROMA_E_ALIGN, "%s: x must be 16-byte aligned", fn);
   long off[WA_N];
   layout_ap(P, N, iters, off);
-  const char* w = static_cast<const char*>(ws);
-  auto sel = ap_select_kernel<SCORE_MSAC>;
-  if (scoring == SCORE_MAGSAC) sel = ap_select_kernel<SCORE_MAGSAC>;
-  hipLaunchKernelGGL(sel, dim3(P), dim3(AP_THREADS), 0, static_cast<hipStream_t>(stream), X, (const double2*)x, K,
-                     (const double*)(w + off[WS_NORM]), (const float4*)(w + off[WS_PTS]), (const float*)(w + off[WA_PV]),
-                     (const double*)(w + off[WS_MODELS]), (const double*)(w + off[WA_TVEC]), (const double*)(w + off[WS_COST]), N,
-                     iters * AP_R, threshold * threshold, lo_iters, R, t, mask);
+  const Regions r = regions(ws, off);
+  const auto sel = by_scoring(scoring, ap_select_kernel<SCORE_MSAC>, ap_select_kernel<SCORE_MAGSAC>);
+  hipLaunchKernelGGL(sel, dim3(P), dim3(AP_THREADS), 0, static_cast<hipStream_t>(stream), X, (const double2*)x, K, r.norm, r.pts,
+                     region<float>(ws, off, WA_PV), r.models, region<double>(ws, off, WA_TVEC), r.cost, N, iters * AP_R,
+                     threshold * threshold, lo_iters, R, t, mask);
   return check_launch(fn);
 }
 

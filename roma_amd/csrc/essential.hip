@@ -53,7 +53,6 @@ namespace {
 constexpr int E_S = 5, E_R = 10;
 constexpr int GROUP = 32, GROUPS = 8;                 // lanes per sample, samples per 256-thread block
 constexpr int BISECT_INNER = 32, BISECT_FINAL = 50, NEWTON_FINAL = 2, POLISH_ITERS = 3;
-constexpr uint32_t STAGE_E = 4u;
 
 // xh: (P,N,4) fp64 calibrated (xa, ya, xb, yb); pts: the fp32 copy; norm: (0, 0, 1, 0) twice
 __global__ __launch_bounds__(256) void calibrate_kernel(const double* __restrict__ xa, const double* __restrict__ xb,
@@ -844,12 +843,8 @@ long layout_e(int P, int N, int iters, long* off) {
 int check_args_e(const char* fn, const void* xa, const void* xb, const void* Ka, const void* Kb, const void* ws, int P, int N,
                  int iters, float threshold, long ws_bytes) {
   ROMA_REQUIRE(xa && xb && Ka && Kb && ws, ROMA_E_ARG, "%s: null pointer", fn);
-  const int rc = check_shape(fn, P, N, iters, E_S);
-  if (rc) return rc;
-  ROMA_REQUIRE(((long)P * iters + GROUPS - 1) / GROUPS <= 0x7FFFFFFFL, ROMA_E_SHAPE, "%s: P * iters = %ld samples in one call", fn,
-               (long)P * iters);
-  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
-  return check_workspace(fn, ws_bytes, layout_e(P, N, iters, nullptr));
+  const int rc = check_problem(fn, P, N, iters, E_S, GROUPS, threshold);
+  return rc ? rc : check_workspace(fn, ws_bytes, layout_e(P, N, iters, nullptr));
 }
 
 }  // namespace
@@ -873,36 +868,23 @@ int essential_hypotheses(const char* fn, const double* xa, const double* xb, con
   if (rc) return rc;
   rc = check_scoring(fn, scoring);
   if (rc) return rc;
-  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "%s: negative pair offset %d", fn, p0);
+  rc = check_pair_offset(fn, p0);
+  if (rc) return rc;
   long off[WE_N];
   layout_e(P, N, iters, off);
-  char* w = static_cast<char*>(ws);
-  double* norm = (double*)(w + off[WS_NORM]);
-  float* pts = (float*)(w + off[WS_PTS]);
-  int* samples = (int*)(w + off[WS_SAMPLES]);
-  double* models = (double*)(w + off[WS_MODELS]);
-  int* valid = (int*)(w + off[WS_VALID]);
-  float* slab_cost = (float*)(w + off[WS_SLAB_COST]);
-  int* slab_cnt = (int*)(w + off[WS_SLAB_CNT]);
-  double* cost = (double*)(w + off[WS_COST]);
-  int* count = (int*)(w + off[WS_COUNT]);
-  double* xh = (double*)(w + off[WE_XH]);
+  const Regions r = regions(ws, off);
+  double* xh = region<double>(ws, off, WE_XH);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int M = iters * E_R, C = (N + CHUNK - 1) / CHUNK;
-  const uint32_t sstream = fmix32((uint32_t)seed ^ (STAGE_E * 0x9E3779B9u));
+  const uint32_t sstream = sample_stream(seed, STAGE_E);
   const float t2 = threshold * threshold;
-  const long nt = (long)P * iters;
-  const dim3 gm((unsigned)((nt + GROUPS - 1) / GROUPS)), gs((unsigned)((M + 255) / 256), (unsigned)C, (unsigned)P);
-  const dim3 gr((unsigned)(((long)P * M + 255) / 256));
-  hipLaunchKernelGGL(calibrate_kernel, dim3(P), dim3(256), 0, st, xa, xb, Ka, Kb, N, norm, pts, xh);
-  hipLaunchKernelGGL(five_point_kernel, gm, dim3(256), 0, st, (const double*)xh, (const float*)pts, P, N, iters, sstream, p0, samples,
-                     models, valid);
-  auto score = score_kernel<KIND_F, SCORE_MSAC>;
-  if (scoring == SCORE_MAGSAC) score = score_kernel<KIND_F, SCORE_MAGSAC>;
-  hipLaunchKernelGGL(score, gs, dim3(256), 0, st, (const float4*)pts, (const double*)norm, (const double*)models, (const int*)valid, N, M,
-                     t2, slab_cost, slab_cnt);
-  hipLaunchKernelGGL(reduce_kernel, gr, dim3(256), 0, st, (const float*)slab_cost, (const int*)slab_cnt, (const int*)valid, P, M, C,
-                     cost, count);
+  const Grids g = ransac_grids(P, N, iters, E_R, GROUPS);
+  hipLaunchKernelGGL(calibrate_kernel, dim3(P), dim3(256), 0, st, xa, xb, Ka, Kb, N, r.norm, (float*)r.pts, xh);
+  hipLaunchKernelGGL(five_point_kernel, g.solve, dim3(256), 0, st, xh, (const float*)r.pts, P, N, iters, sstream, p0, r.samples, r.models,
+                     r.valid);
+  const auto score = by_scoring(scoring, score_kernel<KIND_F, SCORE_MSAC>, score_kernel<KIND_F, SCORE_MAGSAC>);
+  hipLaunchKernelGGL(score, g.score, dim3(256), 0, st, r.pts, r.norm, r.models, r.valid, N, M, t2, r.slab_cost, r.slab_cnt);
+  hipLaunchKernelGGL(reduce_kernel, g.reduce, dim3(256), 0, st, r.slab_cost, r.slab_cnt, r.valid, P, M, C, r.cost, r.count);
   return check_launch(fn);
 }
 
@@ -914,14 +896,13 @@ int essential_select(const char* fn, const double* xa, const double* xb, const d
   ROMA_REQUIRE(E && mask, ROMA_E_ARG, "%s: null pointer", fn);
   rc = check_scoring(fn, scoring);
   if (rc) return rc;
-  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "%s: negative lo_iters %d", fn, lo_iters);
+  rc = check_lo_iters(fn, lo_iters);
+  if (rc) return rc;
   long off[WE_N];
   layout_e(P, N, iters, off);
-  const char* w = static_cast<const char*>(ws);
-  auto sel = essential_select_kernel<SCORE_MSAC>;
-  if (scoring == SCORE_MAGSAC) sel = essential_select_kernel<SCORE_MAGSAC>;
-  hipLaunchKernelGGL(sel, dim3(P), dim3(256), 0, static_cast<hipStream_t>(stream), (const double*)(w + off[WE_XH]),
-                     (const float4*)(w + off[WS_PTS]), (const double*)(w + off[WS_MODELS]), (const double*)(w + off[WS_COST]), N,
+  const Regions r = regions(ws, off);
+  const auto sel = by_scoring(scoring, essential_select_kernel<SCORE_MSAC>, essential_select_kernel<SCORE_MAGSAC>);
+  hipLaunchKernelGGL(sel, dim3(P), dim3(256), 0, static_cast<hipStream_t>(stream), region<double>(ws, off, WE_XH), r.pts, r.models, r.cost, N,
                      iters * E_R, threshold * threshold, lo_iters, E, mask);
   return check_launch(fn);
 }

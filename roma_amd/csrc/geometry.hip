@@ -26,8 +26,8 @@
 // |entry| of the system) rejects the sample.  H samples are also rejected when any 3 of the 4 points are collinear in either
 // image: |(b - a) x (c - a)| <= 1e-6 |b - a| |c - a| (normalised coordinates).
 //
-// Shared code: ransac_common.h has the scoring (score_kernel, reduce_kernel, block_score), the workspace layout and the checks
-// that essential.hip uses too; twoview_math.h the fp64 helpers (elimination, jacobi_lds, Norm / to_pixels) that the refinement
+// Shared code: ransac_common.h has the scoring (score_kernel, reduce_kernel, block_score), the workspace layout, the host helpers
+// and the checks that essential.hip, absolute_pose.hip and similarity.hip use too; twoview_math.h the fp64 helpers (elimination, jacobi_lds, Norm / to_pixels) that the refinement
 // kernels use as well.  Steps 1 and 2 of select_kernel are repeated in essential_select_kernel, statement for statement.
 #include "ransac_common.h"
 
@@ -520,41 +520,32 @@ int ransac_hypotheses(const char* fn, int kind, const double* xa, const double* 
                       int scoring, unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
   int rc = check_args(fn, kind, xa, xb, ws, P, N, iters, ws_bytes);
   if (rc) return rc;
-  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
+  rc = check_threshold(fn, threshold);
+  if (rc) return rc;
   rc = check_scoring(fn, scoring);
   if (rc) return rc;
-  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "%s: negative pair offset %d", fn, p0);
+  rc = check_pair_offset(fn, p0);
+  if (rc) return rc;
   long off[WS_N];
   layout(kind, P, N, iters, off);
-  char* w = static_cast<char*>(ws);
-  double* norm = (double*)(w + off[WS_NORM]);
-  float* pts = (float*)(w + off[WS_PTS]);
-  int* samples = (int*)(w + off[WS_SAMPLES]);
-  double* models = (double*)(w + off[WS_MODELS]);
-  int* valid = (int*)(w + off[WS_VALID]);
-  float* slab_cost = (float*)(w + off[WS_SLAB_COST]);
-  int* slab_cnt = (int*)(w + off[WS_SLAB_CNT]);
-  double* cost = (double*)(w + off[WS_COST]);
-  int* count = (int*)(w + off[WS_COUNT]);
+  const Regions r = regions(ws, off);
+  float* pts = (float*)r.pts;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int R = kind == KIND_F ? 3 : 1, M = iters * R, C = (N + CHUNK - 1) / CHUNK;
-  const uint32_t stage = kind == KIND_F ? 2u : 3u;
-  const uint32_t sstream = fmix32((uint32_t)seed ^ (stage * 0x9E3779B9u));
+  const uint32_t sstream = sample_stream(seed, kind == KIND_F ? STAGE_F : STAGE_H);
   const float t2 = threshold * threshold;
-  hipLaunchKernelGGL(normalize_kernel, dim3(P, 2), dim3(256), 0, st, xa, xb, N, norm, pts);
-  const long nt = (long)P * iters;
-  const dim3 gm((unsigned)((nt + 127) / 128)), gs((unsigned)((M + 255) / 256), (unsigned)C, (unsigned)P);
-  const dim3 gr((unsigned)(((long)P * M + 255) / 256));
+  const Grids g = ransac_grids(P, N, iters, R, 128);
+  hipLaunchKernelGGL(normalize_kernel, dim3(P, 2), dim3(256), 0, st, xa, xb, N, r.norm, pts);
   if (kind == KIND_F)
-    hipLaunchKernelGGL(minimal_kernel<KIND_F>, gm, dim3(128), 0, st, xa, xb, norm, pts, P, N, iters, sstream, p0, samples, models, valid);
+    hipLaunchKernelGGL(minimal_kernel<KIND_F>, g.solve, dim3(128), 0, st, xa, xb, r.norm, pts, P, N, iters, sstream, p0, r.samples, r.models,
+                       r.valid);
   else
-    hipLaunchKernelGGL(minimal_kernel<KIND_H>, gm, dim3(128), 0, st, xa, xb, norm, pts, P, N, iters, sstream, p0, samples, models, valid);
-  auto score = score_kernel<KIND_F, SCORE_MSAC>;
-  if (kind == KIND_F && scoring == SCORE_MAGSAC) score = score_kernel<KIND_F, SCORE_MAGSAC>;
-  if (kind == KIND_H) score = scoring == SCORE_MAGSAC ? score_kernel<KIND_H, SCORE_MAGSAC> : score_kernel<KIND_H, SCORE_MSAC>;
-  hipLaunchKernelGGL(score, gs, dim3(256), 0, st, (const float4*)pts, (const double*)norm, (const double*)models, (const int*)valid, N, M,
-                     t2, slab_cost, slab_cnt);
-  hipLaunchKernelGGL(reduce_kernel, gr, dim3(256), 0, st, slab_cost, slab_cnt, valid, P, M, C, cost, count);
+    hipLaunchKernelGGL(minimal_kernel<KIND_H>, g.solve, dim3(128), 0, st, xa, xb, r.norm, pts, P, N, iters, sstream, p0, r.samples, r.models,
+                       r.valid);
+  const auto score = kind == KIND_F ? by_scoring(scoring, score_kernel<KIND_F, SCORE_MSAC>, score_kernel<KIND_F, SCORE_MAGSAC>)
+                                    : by_scoring(scoring, score_kernel<KIND_H, SCORE_MSAC>, score_kernel<KIND_H, SCORE_MAGSAC>);
+  hipLaunchKernelGGL(score, g.score, dim3(256), 0, st, r.pts, r.norm, r.models, r.valid, N, M, t2, r.slab_cost, r.slab_cnt);
+  hipLaunchKernelGGL(reduce_kernel, g.reduce, dim3(256), 0, st, r.slab_cost, r.slab_cnt, r.valid, P, M, C, r.cost, r.count);
   return check_launch(fn);
 }
 
@@ -563,24 +554,21 @@ int ransac_select(const char* fn, int kind, const double* xa, const double* xb, 
   int rc = check_args(fn, kind, xa, xb, ws, P, N, iters, ws_bytes);
   if (rc) return rc;
   ROMA_REQUIRE(model && mask, ROMA_E_ARG, "%s: null pointer", fn);
-  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
+  rc = check_threshold(fn, threshold);
+  if (rc) return rc;
   rc = check_scoring(fn, scoring);
   if (rc) return rc;
-  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "%s: negative lo_iters %d", fn, lo_iters);
+  rc = check_lo_iters(fn, lo_iters);
+  if (rc) return rc;
   long off[WS_N];
   layout(kind, P, N, iters, off);
-  const char* w = static_cast<const char*>(ws);
-  const float4* pts = (const float4*)(w + off[WS_PTS]);
-  const double* norm = (const double*)(w + off[WS_NORM]);
-  const double* models = (const double*)(w + off[WS_MODELS]);
-  const double* cost = (const double*)(w + off[WS_COST]);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Regions r = regions(ws, off);
   const int M = iters * (kind == KIND_F ? 3 : 1);
   const float t2 = threshold * threshold;
-  auto sel = select_kernel<KIND_F, SCORE_MSAC>;
-  if (kind == KIND_F && scoring == SCORE_MAGSAC) sel = select_kernel<KIND_F, SCORE_MAGSAC>;
-  if (kind == KIND_H) sel = scoring == SCORE_MAGSAC ? select_kernel<KIND_H, SCORE_MAGSAC> : select_kernel<KIND_H, SCORE_MSAC>;
-  hipLaunchKernelGGL(sel, dim3(P), dim3(256), 0, st, xa, xb, pts, norm, models, cost, N, M, t2, lo_iters, model, mask);
+  const auto sel = kind == KIND_F ? by_scoring(scoring, select_kernel<KIND_F, SCORE_MSAC>, select_kernel<KIND_F, SCORE_MAGSAC>)
+                                  : by_scoring(scoring, select_kernel<KIND_H, SCORE_MSAC>, select_kernel<KIND_H, SCORE_MAGSAC>);
+  hipLaunchKernelGGL(sel, dim3(P), dim3(256), 0, static_cast<hipStream_t>(stream), xa, xb, r.pts, r.norm, r.models, r.cost, N, M, t2,
+                     lo_iters, model, mask);
   return check_launch(fn);
 }
 

@@ -1,7 +1,11 @@
-// What the RANSAC translation units share (geometry.hip: F / H, essential.hip: E) on top of the fp64 helpers of twoview_math.h: the
-// counter-hash of the sample draw, fp32 scoring of every slot (score_kernel / reduce_kernel, no atomics; MSAC, or MAGSAC++ by the
-// loss and weight tables of magsac_table.h), the block-wide re-score of the select kernels, the workspace layout and the argument
-// checks of the entry points.  geometry.hip's header pins the draw and the tolerances.  DESIGN.md §3.4.
+// What the RANSAC translation units share (geometry.hip: F / H, essential.hip: E, absolute_pose.hip, similarity.hip) on top of the
+// fp64 helpers of twoview_math.h.  Device: the counter-hash of the sample draw and, where it compiles to the written-out loop,
+// the draw itself (draw_sample); fp32 scoring of every slot (score_kernel / reduce_kernel, no atomics; MSAC, or MAGSAC++ by the
+// loss and weight tables of magsac_table.h; absolute pose and similarity have score kernels of their own around their point error,
+// and all four use reduce_kernel); the block-wide re-score of every select kernel (block_cost).  Host: the workspace layout and
+// the typed pointers to its nine common regions, the stream of a call's draw with the stage of each estimator, the grids, the
+// choice of a kernel's MSAC or MAGSAC++ instance and the argument checks of the entry points.  geometry.hip's header pins the draw
+// and the tolerances.  DESIGN.md §3.4.
 // The refinement kernels (pose_refine.hip, fundamental_refine.hip, homography_refine.hip) score nothing and include twoview_math.h
 // alone.
 #pragma once
@@ -18,6 +22,29 @@ constexpr double COLLINEAR_TOL = 1e-6;
 __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
   h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
   return h;
+}
+
+// The sample draw (geometry.hip's header pins it): S distinct usable indices for sample h of pair `pair`, the pair's index in the
+// whole call; ok = all S were found.  usable(i): point i may be sampled.  Used where it compiles to the written-out loop
+// (p3p_kernel, sim_solve_kernel); minimal_kernel and five_point_kernel keep that loop (profiles/ransac_shared_code_isa.txt).
+template <int S, typename Usable>
+__device__ __forceinline__ void draw_sample(uint32_t stream, uint32_t pair, int iters, int h, int N, Usable usable, int* idx, bool& ok) {
+  ok = true;
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    const uint32_t ctr = ((pair * (uint32_t)iters + (uint32_t)h) * 8u + (uint32_t)k);
+    int got = -1;
+    for (uint32_t att = 0; att < 16; ++att) {
+      const uint32_t hs = fmix32(stream + ctr * 0x9E3779B1u + att * 0x7FEB352Du);
+      const int i = (int)(((uint64_t)hs * (uint64_t)(uint32_t)N) >> 32);
+      bool good = usable(i);
+#pragma unroll
+      for (int j = 0; j < k; ++j) good = good && idx[j] != i;
+      if (good) { got = i; break; }
+    }
+    idx[k] = got;
+    ok = ok && got >= 0;
+  }
 }
 
 template <int KIND> struct Kind;
@@ -119,6 +146,67 @@ inline int check_workspace(const char* fn, long ws_bytes, long need) {
   ROMA_REQUIRE(ws_bytes >= need, ROMA_E_ARG, "%s: workspace of %ld bytes, need %ld", fn, ws_bytes, need);
   return 0;
 }
+inline int check_threshold(const char* fn, float threshold) {
+  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
+  return 0;
+}
+// The checks of a *_hypotheses / *_select entry point behind its null-pointer test, in the order of essential.hip, absolute_pose.hip
+// and similarity.hip: shape, the solver's grid (per_block samples per workgroup), threshold.  geometry.hip checks the workspace
+// before the threshold and has no grid limit, so it calls the pieces itself.
+inline int check_problem(const char* fn, int P, int N, int iters, int smin, int per_block, float threshold) {
+  const int rc = check_shape(fn, P, N, iters, smin);
+  if (rc) return rc;
+  ROMA_REQUIRE(((long)P * iters + per_block - 1) / per_block <= 0x7FFFFFFFL, ROMA_E_SHAPE, "%s: P * iters = %ld samples in one call", fn,
+               (long)P * iters);
+  return check_threshold(fn, threshold);
+}
+// ... and the last check of each: the pair offset of *_hypotheses, the rounds of *_select
+inline int check_pair_offset(const char* fn, int p0) {
+  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "%s: negative pair offset %d", fn, p0);
+  return 0;
+}
+inline int check_lo_iters(const char* fn, int lo_iters) {
+  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "%s: negative lo_iters %d", fn, lo_iters);
+  return 0;
+}
+
+// The nine common regions of a workspace as typed pointers, from ws_layout's offsets.  *_select only reads through them.
+struct Regions {
+  double* norm;
+  float4* pts;
+  int* samples;
+  double* models;
+  int* valid;
+  float* slab_cost;
+  int* slab_cnt;
+  double* cost;
+  int* count;
+};
+inline Regions regions(const void* ws, const long* off) {
+  char* w = static_cast<char*>(const_cast<void*>(ws));
+  return {(double*)(w + off[WS_NORM]),      (float4*)(w + off[WS_PTS]),     (int*)(w + off[WS_SAMPLES]),
+          (double*)(w + off[WS_MODELS]),    (int*)(w + off[WS_VALID]),      (float*)(w + off[WS_SLAB_COST]),
+          (int*)(w + off[WS_SLAB_CNT]),     (double*)(w + off[WS_COST]),    (int*)(w + off[WS_COUNT])};
+}
+template <typename T> inline T* region(const void* ws, const long* off, int i) {      // an estimator's own region
+  return (T*)(static_cast<char*>(const_cast<void*>(ws)) + off[i]);
+}
+
+// The stream of a call's draw (geometry.hip's header): one stage per estimator, so that no two draw the same samples from one seed
+constexpr uint32_t STAGE_F = 2u, STAGE_H = 3u, STAGE_E = 4u, STAGE_AP = 5u, STAGE_SIM = 6u;
+inline uint32_t sample_stream(unsigned seed, uint32_t stage) { return fmix32((uint32_t)seed ^ (stage * 0x9E3779B9u)); }
+
+// The grids of one *_hypotheses call: the minimal solver (per_block samples per workgroup), the scoring (256 slots x one chunk x one
+// pair per workgroup) and the reduction (256 slots per workgroup).  R = slots per sample.
+struct Grids { dim3 solve, score, reduce; };
+inline Grids ransac_grids(int P, int N, int iters, int R, int per_block) {
+  const long nt = (long)P * iters, M = (long)iters * R;
+  return {dim3((unsigned)((nt + per_block - 1) / per_block)), dim3((unsigned)((M + 255) / 256), (unsigned)((N + CHUNK - 1) / CHUNK), (unsigned)P),
+          dim3((unsigned)((P * M + 255) / 256))};
+}
+
+// kernel<..., SCORE_MSAC> or kernel<..., SCORE_MAGSAC>: the caller names both instances, `scoring` (checked) picks
+template <typename K> inline K by_scoring(int scoring, K msac, K magsac) { return scoring == SCORE_MAGSAC ? magsac : msac; }
 
 // slab_cost / slab_cnt: (P, S, M) with M = iters * R slots and S = ceil(N / CHUNK) chunks.  SCORE_MAGSAC: the partial cost is
 // threshold^2 * (outliers of the chunk + sum of L over its inliers).  The loss nodes 0..1023 sit in LDS beside the points (4 KB: with
@@ -194,18 +282,15 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ s
 
 // ---------------------------------------------------------------------------------------------- selection + local optimisation
 
-// Cost (fp32 errors, fp64 sum in a fixed tree) and inlier count of the model in LDS `mdl` over the pair's N points.
-template <int KIND, int SCORE>
-__device__ void block_score(const double* mdl, const float4* pq, int N, float ka, float kb, float t2, double* dred, int* ired,
-                            double& cost, int& cnt) {
+// Cost (fp32 errors, fp64 sum in a fixed tree) and inlier count of one model over the pair's N points, by the 256 threads of a
+// block: err(i) = squared error of point i under it.  The re-score of every select kernel.
+template <int SCORE, typename Err>
+__device__ __forceinline__ void block_cost(int N, float t2, Err err, double* dred, int* ired, double& cost, int& cnt) {
   const int tid = threadIdx.x;
-  float m[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) m[i] = (float)mdl[i];
   double c = 0.0;
   int n = 0;
   for (int i = tid; i < N; i += 256) {
-    const float e = point_error<KIND>(m, pq[i], ka, kb);
+    const float e = err(i);
     const bool in = e < t2;
     n += in ? 1 : 0;
     if constexpr (SCORE == SCORE_MSAC) c += (double)(in ? e : t2);
@@ -222,6 +307,16 @@ __device__ void block_score(const double* mdl, const float4* pq, int N, float ka
   cost = dred[0];
   cnt = ired[0];
   __syncthreads();
+}
+
+// ... of the model in LDS `mdl` (F, H, E)
+template <int KIND, int SCORE>
+__device__ void block_score(const double* mdl, const float4* pq, int N, float ka, float kb, float t2, double* dred, int* ired,
+                            double& cost, int& cnt) {
+  float m[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) m[i] = (float)mdl[i];
+  block_cost<SCORE>(N, t2, [&](int i) { return point_error<KIND>(m, pq[i], ka, kb); }, dred, ired, cost, cnt);
 }
 
 }  // namespace

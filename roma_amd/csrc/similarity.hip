@@ -46,7 +46,6 @@ namespace roma {
 namespace {
 
 constexpr int SIM_S = 3, SIM_R = 1;
-constexpr uint32_t STAGE_SIM = 6u;
 constexpr int SIM_SOLVE_THREADS = 128;
 constexpr int SIM_THREADS = 256, SIM_WAVES = SIM_THREADS / 64;
 constexpr int SIM_NSUM = 20;                                    // the 18 sums + cost + count
@@ -306,23 +305,8 @@ __global__ __launch_bounds__(SIM_SOLVE_THREADS) void sim_solve_kernel(const doub
   const size_t base = (size_t)p * N;
 
   int idx[SIM_S];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < SIM_S; ++k) {
-    const uint32_t ctr = (((uint32_t)(p0 + p) * (uint32_t)iters + (uint32_t)h) * 8u + (uint32_t)k);
-    int got = -1;
-    for (uint32_t att = 0; att < 16; ++att) {
-      const uint32_t hs = fmix32(stream + ctr * 0x9E3779B1u + att * 0x7FEB352Du);
-      const int i = (int)(((uint64_t)hs * (uint64_t)(uint32_t)N) >> 32);
-      const float v = pts[base + i].x;
-      bool good = v == v;
-#pragma unroll
-      for (int j = 0; j < k; ++j) good = good && idx[j] != i;
-      if (good) { got = i; break; }
-    }
-    idx[k] = got;
-    ok = ok && got >= 0;
-  }
+  bool ok;
+  draw_sample<SIM_S>(stream, (uint32_t)(p0 + p), iters, h, N, [&](int i) { const float v = pts[base + i].x; return v == v; }, idx, ok);
 #pragma unroll
   for (int k = 0; k < SIM_S; ++k) samples[(size_t)t * SIM_S + k] = ok ? idx[k] : -1;
 
@@ -440,33 +424,13 @@ __global__ __launch_bounds__(256) void sim_score_kernel(const float4* __restrict
   slab_cnt[o] = cnt;
 }
 
-// Cost (fp32 errors, fp64 sum in a fixed tree) and inlier count of the model over the pair's N records: block_score of ransac_common.h
+// Cost and inlier count of the model over the pair's N records: block_cost of ransac_common.h
 template <int SCORE>
 __device__ void sim_block_score(const Sim& mdl, const float4* pq, const float2* pyq, int N, float t2, double* dred, int* ired,
                                 double& cost, int& cnt) {
-  const int tid = threadIdx.x;
   float m[12];
   compose_similarity(mdl, m);
-  double c = 0.0;
-  int n = 0;
-  for (int i = tid; i < N; i += 256) {
-    const float e = sim_point_error(m, pq[i], pyq[i]);
-    const bool in = e < t2;
-    n += in ? 1 : 0;
-    if constexpr (SCORE == SCORE_MSAC) c += (double)(in ? e : t2);
-    else c += (double)(in ? magsac_lookup(magsac_loss_cells, e, (float)MAGSAC_CELLS / t2) : 1.f);
-  }
-  if constexpr (SCORE == SCORE_MAGSAC) c *= (double)t2;
-  dred[tid] = c;
-  ired[tid] = n;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) { dred[tid] += dred[tid + o]; ired[tid] += ired[tid + o]; }
-    __syncthreads();
-  }
-  cost = dred[0];
-  cnt = ired[0];
-  __syncthreads();
+  block_cost<SCORE>(N, t2, [&](int i) { return sim_point_error(m, pq[i], pyq[i]); }, dred, ired, cost, cnt);
 }
 
 // ------------------------------------------------------------------------------------------ selection + local optimisation
@@ -675,12 +639,9 @@ long layout_sim(int P, int N, int iters, long* off) {
 int check_args_sim(const char* fn, const void* X, const void* Y, const void* ws, int P, int N, int iters, float threshold, int scoring,
                    long ws_bytes) {
   ROMA_REQUIRE(X && Y && ws, ROMA_E_ARG, "%s: null pointer", fn);
-  int rc = check_shape(fn, P, N, iters, SIM_S);
+  int rc = check_problem(fn, P, N, iters, SIM_S, SIM_SOLVE_THREADS, threshold);
   if (rc) return rc;
-  ROMA_REQUIRE(((long)P * iters + SIM_SOLVE_THREADS - 1) / SIM_SOLVE_THREADS <= 0x7FFFFFFFL, ROMA_E_SHAPE,
-               "%s: P * iters = %ld samples in one call", fn, (long)P * iters);
-  ROMA_REQUIRE(threshold > 0.f && threshold < 1e18f, ROMA_E_ARG, "%s: threshold must be positive, got %g", fn, (double)threshold);
-  rc = check_scoring(fn, scoring);
+  rc = check_scoring(fn, scoring);                               // before the workspace here, behind it in the other three files
   if (rc) return rc;
   rc = check_workspace(fn, ws_bytes, layout_sim(P, N, iters, nullptr));
   if (rc) return rc;
@@ -705,40 +666,27 @@ extern "C" long roma_similarity_workspace(int P, int N, int iters, long* offsets
 extern "C" int roma_similarity_hypotheses(const double* X, const double* Y, int P, int N, int iters, float threshold, int scoring,
                                           int with_scale, unsigned seed, int p0, void* ws, long ws_bytes, void* stream) {
   const char* fn = __func__;
-  const int rc = check_args_sim(fn, X, Y, ws, P, N, iters, threshold, scoring, ws_bytes);
+  int rc = check_args_sim(fn, X, Y, ws, P, N, iters, threshold, scoring, ws_bytes);
   if (rc) return rc;
-  ROMA_REQUIRE(p0 >= 0, ROMA_E_ARG, "%s: negative pair offset %d", fn, p0);
+  rc = check_pair_offset(fn, p0);
+  if (rc) return rc;
   long off[WM_N];
   layout_sim(P, N, iters, off);
-  char* w = static_cast<char*>(ws);
-  double* norm = (double*)(w + off[WS_NORM]);
-  float4* pts = (float4*)(w + off[WS_PTS]);
-  int* samples = (int*)(w + off[WS_SAMPLES]);
-  double* models = (double*)(w + off[WS_MODELS]);
-  int* valid = (int*)(w + off[WS_VALID]);
-  float* slab_cost = (float*)(w + off[WS_SLAB_COST]);
-  int* slab_cnt = (int*)(w + off[WS_SLAB_CNT]);
-  double* cost = (double*)(w + off[WS_COST]);
-  int* count = (int*)(w + off[WS_COUNT]);
-  double* ts = (double*)(w + off[WM_TS]);
-  float2* py = (float2*)(w + off[WM_PY]);
-  double* xn = (double*)(w + off[WM_XN]);
+  const Regions r = regions(ws, off);
+  double* ts = region<double>(ws, off, WM_TS);
+  float2* py = region<float2>(ws, off, WM_PY);
+  double* xn = region<double>(ws, off, WM_XN);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int M = iters * SIM_R, C = (N + CHUNK - 1) / CHUNK;
-  const uint32_t sstream = fmix32((uint32_t)seed ^ (STAGE_SIM * 0x9E3779B9u));
+  const uint32_t sstream = sample_stream(seed, STAGE_SIM);
   const float thr2 = threshold * threshold;                      // in Y units; the kernels scale it by the pair's sY^2
-  const long nt = (long)P * iters;
-  const dim3 gm((unsigned)((nt + SIM_SOLVE_THREADS - 1) / SIM_SOLVE_THREADS)), gs((unsigned)((M + 255) / 256), (unsigned)C, (unsigned)P);
-  const dim3 gr((unsigned)(((long)P * M + 255) / 256));
-  hipLaunchKernelGGL(sim_prepare_kernel, dim3(P), dim3(256), 0, st, X, Y, N, with_scale, norm, pts, py, xn);
-  hipLaunchKernelGGL(sim_solve_kernel, gm, dim3(SIM_SOLVE_THREADS), 0, st, (const double*)xn, (const float4*)pts, P, N, iters, sstream, p0,
-                     with_scale, samples, models, ts, valid);
-  auto score = sim_score_kernel<SCORE_MSAC>;
-  if (scoring == SCORE_MAGSAC) score = sim_score_kernel<SCORE_MAGSAC>;
-  hipLaunchKernelGGL(score, gs, dim3(256), 0, st, (const float4*)pts, (const float2*)py, (const double*)models, (const double*)ts,
-                     (const int*)valid, (const double*)norm, N, M, thr2, slab_cost, slab_cnt);
-  hipLaunchKernelGGL(reduce_kernel, gr, dim3(256), 0, st, (const float*)slab_cost, (const int*)slab_cnt, (const int*)valid, P, M, C,
-                     cost, count);
+  const Grids g = ransac_grids(P, N, iters, SIM_R, SIM_SOLVE_THREADS);
+  hipLaunchKernelGGL(sim_prepare_kernel, dim3(P), dim3(256), 0, st, X, Y, N, with_scale, r.norm, r.pts, py, xn);
+  hipLaunchKernelGGL(sim_solve_kernel, g.solve, dim3(SIM_SOLVE_THREADS), 0, st, xn, r.pts, P, N, iters, sstream, p0, with_scale, r.samples,
+                     r.models, ts, r.valid);
+  const auto score = by_scoring(scoring, sim_score_kernel<SCORE_MSAC>, sim_score_kernel<SCORE_MAGSAC>);
+  hipLaunchKernelGGL(score, g.score, dim3(256), 0, st, r.pts, py, r.models, ts, r.valid, r.norm, N, M, thr2, r.slab_cost, r.slab_cnt);
+  hipLaunchKernelGGL(reduce_kernel, g.reduce, dim3(256), 0, st, r.slab_cost, r.slab_cnt, r.valid, P, M, C, r.cost, r.count);
   return check_launch(fn);
 }
 
@@ -746,20 +694,19 @@ extern "C" int roma_similarity_select(const double* X, const double* Y, int P, i
                                       int with_scale, int lo_iters, const void* ws, long ws_bytes, double* s, double* R, double* t,
                                       unsigned char* mask, int* valid, void* stream) {
   const char* fn = __func__;
-  const int rc = check_args_sim(fn, X, Y, ws, P, N, iters, threshold, scoring, ws_bytes);
+  int rc = check_args_sim(fn, X, Y, ws, P, N, iters, threshold, scoring, ws_bytes);
   if (rc) return rc;
   ROMA_REQUIRE(s && R && t && mask && valid, ROMA_E_ARG, "%s: null pointer", fn);
-  ROMA_REQUIRE(lo_iters >= 0, ROMA_E_ARG, "%s: negative lo_iters %d", fn, lo_iters);
+  rc = check_lo_iters(fn, lo_iters);
+  if (rc) return rc;
   long off[WM_N];
   layout_sim(P, N, iters, off);
-  const char* w = static_cast<const char*>(ws);
-  auto sel = sim_select_kernel<SCORE_MSAC>;
-  if (scoring == SCORE_MAGSAC) sel = sim_select_kernel<SCORE_MAGSAC>;
+  const Regions r = regions(ws, off);
+  const auto sel = by_scoring(scoring, sim_select_kernel<SCORE_MSAC>, sim_select_kernel<SCORE_MAGSAC>);
   // X and Y are not read again: the kernel works on the normalised copy that roma_similarity_hypotheses left in the workspace
-  hipLaunchKernelGGL(sel, dim3(P), dim3(SIM_THREADS), 0, static_cast<hipStream_t>(stream), (const double*)(w + off[WS_NORM]),
-                     (const float4*)(w + off[WS_PTS]), (const float2*)(w + off[WM_PY]), (const double*)(w + off[WM_XN]),
-                     (const double*)(w + off[WS_MODELS]), (const double*)(w + off[WM_TS]), (const double*)(w + off[WS_COST]), N,
-                     iters * SIM_R, threshold * threshold, with_scale, lo_iters, s, R, t, mask, valid);
+  hipLaunchKernelGGL(sel, dim3(P), dim3(SIM_THREADS), 0, static_cast<hipStream_t>(stream), r.norm, r.pts, region<float2>(ws, off, WM_PY),
+                     region<double>(ws, off, WM_XN), r.models, region<double>(ws, off, WM_TS), r.cost, N, iters * SIM_R,
+                     threshold * threshold, with_scale, lo_iters, s, R, t, mask, valid);
   return check_launch(fn);
 }
 

@@ -97,14 +97,20 @@ from .ops import _need_gpu, _stream
 
 KIND_F, KIND_H = 0, 1
 KIND_E = 2                            # this module's name for the essential estimator; the C ABI has entry points of its own for it
-_SMIN = {KIND_F: 7, KIND_H: 4, KIND_E: 5}
-_SLOTS = {KIND_F: 3, KIND_H: 1, KIND_E: 10}
+_KIND_AP, _KIND_SIM = 3, 4            # and for absolute pose and 3-D similarity, which have no public name for theirs
 _WORKSPACE_LIMIT = 192 << 20          # workspace bytes of one call; larger batches run in chunks of pairs that share it
-# The C entry points of an estimator: (workspace function, hypotheses entry, select entry, workspace regions, calibrated).  F and H share
-# theirs, which take the kind first; E has its own (calibrated), which take K_A, K_B behind the points and lay out one more region.
-_RANSAC = ("roma_ransac_workspace", "roma_ransac_hypotheses_ex", "roma_ransac_select_ex", 9, False)
-_ENTRIES = {KIND_F: _RANSAC, KIND_H: _RANSAC,
-            KIND_E: ("roma_essential_workspace", "roma_essential_hypotheses_ex", "roma_essential_select_ex", 10, True)}
+# One RANSAC estimator: its C entry points, the regions its workspace function lays out, the points of a minimal sample, the slots
+# (models) per sample, and `lead`, the C arguments in front of the points (the kind, for F and H, which share their entry points).
+# Behind the points come the per-pair constants (K_A, K_B for E, K for absolute pose) and behind `scoring` the scalars of the model
+# (with_scale for similarity): those are values of a call, which _ransac and _inspect take as `consts` and `tail`.
+_Estimator = collections.namedtuple("_Estimator", "workspace hypotheses select regions smin slots lead")
+_ENTRIES = {
+    KIND_F: _Estimator("roma_ransac_workspace", "roma_ransac_hypotheses_ex", "roma_ransac_select_ex", 9, 7, 3, (KIND_F,)),
+    KIND_H: _Estimator("roma_ransac_workspace", "roma_ransac_hypotheses_ex", "roma_ransac_select_ex", 9, 4, 1, (KIND_H,)),
+    KIND_E: _Estimator("roma_essential_workspace", "roma_essential_hypotheses_ex", "roma_essential_select_ex", 10, 5, 10, ()),
+    _KIND_AP: _Estimator("roma_absolute_pose_workspace", "roma_absolute_pose_hypotheses", "roma_absolute_pose_select", 12, 3, 4, ()),
+    _KIND_SIM: _Estimator("roma_similarity_workspace", "roma_similarity_hypotheses", "roma_similarity_select", 12, 3, 1, ()),
+}
 
 
 def _kind(model):
@@ -117,25 +123,34 @@ def _kind(model):
     raise ValueError(f"unknown model {model!r}: 'fundamental', 'homography' or 'essential'")
 
 
-def _points(x_A, x_B, kind):
-    """(N,2) or (P,N,2) fp32/fp64 device tensors -> contiguous (P,N,2) fp64, single-pair flag."""
-    _need_gpu(x_A, x_B)
-    if x_A.shape != x_B.shape:
-        raise ValueError(f"x_A {tuple(x_A.shape)} and x_B {tuple(x_B.shape)} differ in shape")
-    if x_A.dim() not in (2, 3) or x_A.shape[-1] != 2:
-        raise ValueError(f"expected (N,2) or (P,N,2) pixel coordinates, got {tuple(x_A.shape)}")
-    for t in (x_A, x_B):
+def _prepare(a, b, wa, wb, smin, form, what, rows, differ=None, gpu_first=False):
+    """The two point sets of a call, a (N,wa) or (P,N,wa) and b (N,wb) or (P,N,wb), fp32/fp64 device tensors -> contiguous (P,N,wa),
+    (P,N,wb) fp64, single-pair flag.  form / differ: the messages for a wrong shape (formatted with the two shapes), what / rows: the
+    nouns of the dtype and the count message; gpu_first: whether the device is checked before the shapes or after the counts."""
+    if gpu_first:
+        _need_gpu(a, b)
+    if differ and a.shape != b.shape:
+        raise ValueError(differ.format(tuple(a.shape), tuple(b.shape)))
+    if a.dim() not in (2, 3) or a.shape[-1] != wa or b.shape != a.shape[:-1] + (wb,):
+        raise ValueError(form.format(tuple(a.shape), tuple(b.shape)))
+    for t in (a, b):
         if t.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"pixel coordinates must be float32 or float64, got {t.dtype}")
-    single = x_A.dim() == 2
-    P, N = (1, x_A.shape[0]) if single else (x_A.shape[0], x_A.shape[1])
-    if N < _SMIN[kind]:
-        raise ValueError(f"{N} matches, the minimal sample needs {_SMIN[kind]}")
+            raise ValueError(f"{what} must be float32 or float64, got {t.dtype}")
+    single = a.dim() == 2
+    P, N = (1, a.shape[0]) if single else (a.shape[0], a.shape[1])
+    if N < smin:
+        raise ValueError(f"{N} {rows}, the minimal sample needs {smin}")
     if P < 1:
         raise ValueError("empty batch")
-    xa = x_A.reshape(P, N, 2).to(torch.float64).contiguous()
-    xb = x_B.reshape(P, N, 2).to(torch.float64).contiguous()
-    return xa, xb, single
+    if not gpu_first:
+        _need_gpu(a, b)
+    return a.reshape(P, N, wa).to(torch.float64).contiguous(), b.reshape(P, N, wb).to(torch.float64).contiguous(), single
+
+
+def _points(x_A, x_B, kind):
+    """(N,2) or (P,N,2) fp32/fp64 device tensors -> contiguous (P,N,2) fp64, single-pair flag."""
+    return _prepare(x_A, x_B, 2, 2, _ENTRIES[kind].smin, "expected (N,2) or (P,N,2) pixel coordinates, got {0}", "pixel coordinates",
+                    "matches", differ="x_A {0} and x_B {1} differ in shape", gpu_first=True)
 
 
 def _mask(mask, P, N, points=None):
@@ -184,8 +199,8 @@ def _workspace_layout(entry, regions, *shape):
 def workspace_layout(kind, P, N, iters):
     """(total bytes, [region offsets]) of the workspace (include/roma_hip.h: the 9 regions of roma_ransac_workspace, the 10 of
     roma_essential_workspace for KIND_E)."""
-    workspace, _, _, regions, calibrated = _ENTRIES[kind]
-    return _workspace_layout(workspace, regions, *(() if calibrated else (kind,)), P, N, iters)
+    est = _ENTRIES[kind]
+    return _workspace_layout(est.workspace, est.regions, *est.lead, P, N, iters)
 
 
 def _chunks(kind, P, N, iters):
@@ -195,6 +210,16 @@ def _chunks(kind, P, N, iters):
     n = -(-P // most)
     step = -(-P // n)
     return [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
+
+
+def _ap_chunks(P, N, iters):
+    """_chunks for absolute pose, under the name it had when each estimator had a chunker of its own"""
+    return _chunks(_KIND_AP, P, N, iters)
+
+
+def _sim_chunks(P, N, iters):
+    """_chunks for similarity, likewise"""
+    return _chunks(_KIND_SIM, P, N, iters)
 
 
 def _intrinsics(K, P, device, name):
@@ -221,12 +246,32 @@ def _inverse_intrinsics(K):
     return T
 
 
-def _hypotheses(xa, xb, kind, threshold, iters, seed, p0, ws, K=(), score=_lib.SCORE_MSAC):
-    """K: the (K_A, K_B) of these pairs for KIND_E, nothing for F and H"""
-    P, N = xa.shape[0], xa.shape[1]
-    _, entry, _, _, calibrated = _ENTRIES[kind]
-    check(getattr(_lib.load(), entry)(*(() if calibrated else (kind,)), xa.data_ptr(), xb.data_ptr(), *(k.data_ptr() for k in K), P, N, iters,
-                                      float(threshold), score, seed, p0, ws.data_ptr(), ws.numel(), _stream()), entry)
+def _front(kind, a, b, consts, tail, threshold, iters, score):
+    """the C arguments that an estimator's hypotheses and select entries share, up to and including the scalars behind `scoring`"""
+    return (*_ENTRIES[kind].lead, a.data_ptr(), b.data_ptr(), *(c.data_ptr() for c in consts), a.shape[0], a.shape[1], iters,
+            float(threshold), score, *tail)
+
+
+def _hypotheses(kind, a, b, consts, tail, threshold, iters, score, seed, p0, ws):
+    entry = _ENTRIES[kind].hypotheses
+    check(getattr(_lib.load(), entry)(*_front(kind, a, b, consts, tail, threshold, iters, score), seed, p0, ws.data_ptr(), ws.numel(),
+                                      _stream()), entry)
+
+
+def _ransac(kind, a, b, consts, tail, threshold, iters, score, seed, lo_iters, outs):
+    """The RANSAC of every estimator, on prepared inputs: a, b the (P,N,.) fp64 points, consts the per-pair constant tensors (P,...),
+    tail the scalars behind `scoring`, outs the (P,...) tensors the select entry fills, in its order."""
+    select, P, N = _ENTRIES[kind].select, a.shape[0], a.shape[1]
+    lib = _lib.load()
+    chunks = _chunks(kind, P, N, iters)
+    # one workspace, sized for the widest chunk, serves every chunk in stream order (a narrower chunk's layout is no larger)
+    total, _ = workspace_layout(kind, max(p1 - p0 for p0, p1 in chunks), N, iters)
+    ws = torch.empty((total,), dtype=torch.uint8, device=a.device)
+    for p0, p1 in chunks:
+        ca, cb, cc = a[p0:p1], b[p0:p1], [c[p0:p1] for c in consts]
+        _hypotheses(kind, ca, cb, cc, tail, threshold, iters, score, seed, p0, ws)
+        check(getattr(lib, select)(*_front(kind, ca, cb, cc, tail, threshold, iters, score), int(lo_iters), ws.data_ptr(), total,
+                                   *(o[p0:p1].data_ptr() for o in outs), _stream()), select)
 
 
 def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_B=None, scoring="msac"):
@@ -234,22 +279,10 @@ def _estimate(x_A, x_B, kind, threshold, max_iters, seed, lo_iters, K_A=None, K_
     _args(threshold, max_iters, lo_iters)
     xa, xb, single = _points(x_A, x_B, kind)
     P, N = xa.shape[0], xa.shape[1]
-    _, _, select, _, calibrated = _ENTRIES[kind]
-    K = (_intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")) if calibrated else ()
-    iters, seed = int(max_iters), _seed(seed)
+    K = (_intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")) if kind == KIND_E else ()
     model = torch.empty((P, 3, 3), dtype=torch.float64, device=xa.device)
     mask = torch.empty((P, N), dtype=torch.uint8, device=xa.device)
-    lib = _lib.load()
-    chunks = _chunks(kind, P, N, iters)
-    # one workspace, sized for the widest chunk, serves every chunk in stream order (a narrower chunk's layout is no larger)
-    total, _ = workspace_layout(kind, max(b - a for a, b in chunks), N, iters)
-    ws = torch.empty((total,), dtype=torch.uint8, device=xa.device)
-    for a, b in chunks:
-        ca, cb, Kc = xa[a:b], xb[a:b], tuple(k[a:b] for k in K)
-        _hypotheses(ca, cb, kind, threshold, iters, seed, a, ws, Kc, score)
-        check(getattr(lib, select)(*(() if calibrated else (kind,)), ca.data_ptr(), cb.data_ptr(), *(k.data_ptr() for k in Kc), b - a, N,
-                                   iters, float(threshold), score, int(lo_iters), ws.data_ptr(), total, model[a:b].data_ptr(),
-                                   mask[a:b].data_ptr(), _stream()), select)
+    _ransac(kind, xa, xb, K, (), threshold, int(max_iters), score, _seed(seed), lo_iters, (model, mask))
     mask = mask.bool()
     return (model[0], mask[0]) if single else (model, mask)
 
@@ -378,6 +411,20 @@ def _refined(res, info, single, return_info):
     return res + ({"cost": cost[0], "count": count[0], "steps": steps[0]} if single else {"cost": cost, "count": count, "steps": steps},)
 
 
+def _run_refine(entry, inputs, P, N, scalars, *shapes):
+    """A refine_* entry point on prepared (P,...) tensors: entry(inputs (None: a null pointer)..., P, N, scalars..., outputs..., stream).
+    Allocates the outputs every one of them has — an fp64 model tensor (P, *shape) per shape, the (P,N) mask, cost, count, steps — and
+    returns (models..., mask bool), (cost, count, steps)."""
+    dev = inputs[0].device
+    models = [torch.empty((P,) + shape, dtype=torch.float64, device=dev) for shape in shapes]
+    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
+    info = (torch.empty((P,), dtype=torch.float64, device=dev), torch.empty((P,), dtype=torch.int32, device=dev),
+            torch.empty((P,), dtype=torch.int32, device=dev))
+    check(getattr(_lib.load(), entry)(*(None if v is None else v.data_ptr() for v in inputs), P, N, *scalars,
+                                      *(o.data_ptr() for o in (*models, out, *info)), _stream()), entry)
+    return (*models, out.bool()), info
+
+
 def _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask):
     """refine_pose on batched outputs: (R (P,3,3), t (P,3), mask (P,N) bool), (cost (P,) fp64, count (P,) int32, steps (P,) int32), single"""
     _need_gpu(R, t)
@@ -390,18 +437,7 @@ def _refine(R, t, x_A, x_B, K_A, K_B, threshold, iters, mask):
     r0 = R.reshape(P, 3, 3).to(torch.float64).contiguous()
     t0 = t.reshape(P, 3).to(torch.float64).contiguous()
     m = _mask(mask, P, N, x_A)
-    dev = xa.device
-    Ro = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
-    to = torch.empty((P, 3), dtype=torch.float64, device=dev)
-    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
-    cost = torch.empty((P,), dtype=torch.float64, device=dev)
-    count = torch.empty((P,), dtype=torch.int32, device=dev)
-    steps = torch.empty((P,), dtype=torch.int32, device=dev)
-    check(_lib.load().roma_refine_pose(xa.data_ptr(), xb.data_ptr(), Ka.data_ptr(), Kb.data_ptr(), r0.data_ptr(), t0.data_ptr(),
-                                       None if m is None else m.data_ptr(), P, N, float(threshold), int(iters), Ro.data_ptr(),
-                                       to.data_ptr(), out.data_ptr(), cost.data_ptr(), count.data_ptr(), steps.data_ptr(), _stream()),
-          "roma_refine_pose")
-    return (Ro, to, out.bool()), (cost, count, steps), single
+    return _run_refine("roma_refine_pose", (xa, xb, Ka, Kb, r0, t0, m), P, N, (float(threshold), int(iters)), (3, 3), (3,)) + (single,)
 
 
 def refine_pose(R, t, x_A, x_B, K_A, K_B, threshold, iters=15, mask=None, return_info=False):
@@ -430,16 +466,7 @@ def _refine_model(M, x_A, x_B, kind, least, entry, threshold, iters, mask, retur
         raise ValueError(f"{name} {tuple(M.shape)} does not match the points {tuple(x_A.shape)}")
     m0 = M.reshape(P, 3, 3).to(torch.float64).contiguous()
     m = _mask(mask, P, N, x_A)
-    dev = xa.device
-    Mo = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
-    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
-    cost = torch.empty((P,), dtype=torch.float64, device=dev)
-    count = torch.empty((P,), dtype=torch.int32, device=dev)
-    steps = torch.empty((P,), dtype=torch.int32, device=dev)
-    check(getattr(_lib.load(), entry)(xa.data_ptr(), xb.data_ptr(), m0.data_ptr(), None if m is None else m.data_ptr(), P, N,
-                                      float(threshold), int(iters), Mo.data_ptr(), out.data_ptr(), cost.data_ptr(), count.data_ptr(),
-                                      steps.data_ptr(), _stream()), entry)
-    return _refined((Mo, out.bool()), (cost, count, steps), single, return_info)
+    return _refined(*_run_refine(entry, (xa, xb, m0, m), P, N, (float(threshold), int(iters)), (3, 3)), single, return_info)
 
 
 def refine_fundamental(F, x_A, x_B, threshold=3.0, iters=15, mask=None, return_info=False):
@@ -579,6 +606,28 @@ def _view(ws, off, i, dtype, shape):
     return ws[off[i]:off[i] + n * item].view(dtype).reshape(shape)
 
 
+def _inspect(name, kind, a, b, consts, tail, threshold, max_iters, score, seed):
+    """What the inspectors share: one hypotheses call on the whole batch, which `name` refuses beyond _WORKSPACE_LIMIT.  consts() gives
+    the per-pair constant tensors once the batch is accepted; the other arguments as _ransac's.  Returns the views every estimator
+    has — samples (P,iters,smin), valid, cost, count (P,iters,slots) —, view(region, dtype, shape behind P) for the estimator's own,
+    and the constants."""
+    est, P, N, iters = _ENTRIES[kind], a.shape[0], a.shape[1], int(max_iters)
+    total, off = workspace_layout(kind, P, N, iters)
+    if total > _WORKSPACE_LIMIT:
+        raise ValueError(f"{name}: {P} pairs need a {total >> 20} MiB workspace, over the {_WORKSPACE_LIMIT >> 20} MiB "
+                         "limit; call it on fewer pairs")
+    ws = torch.empty((total,), dtype=torch.uint8, device=a.device)
+    consts = consts()
+    _hypotheses(kind, a, b, consts, tail, threshold, iters, score, _seed(seed), 0, ws)
+
+    def view(region, dtype, shape):
+        return _view(ws, off, region, dtype, (P,) + tuple(shape))
+
+    slots = (iters, est.slots)
+    return {"samples": view(2, torch.int32, (iters, est.smin)).clone(), "valid": view(4, torch.int32, slots) != 0,
+            "cost": view(7, torch.float64, slots).clone(), "count": view(8, torch.int32, slots).clone()}, view, consts
+
+
 def minimal_samples(x_A, x_B, model="fundamental", max_iters=10000, seed=0, K_A=None, K_B=None):
     """The indices each minimal sample draws: (P, max_iters, s) int32, s = 7 (F) / 4 (H) / 5 (E), a row of -1 for an invalid sample.
     An inspection helper like score_hypotheses, with its batch limit.  model = "essential" takes the intrinsics (default: identity)."""
@@ -601,37 +650,28 @@ def score_hypotheses(x_A, x_B, model="fundamental", threshold=3.0, max_iters=100
     kind, score = _kind(model), _scoring(scoring)
     _args(threshold, max_iters, 0)
     xa, xb, _ = _points(x_A, x_B, kind)
-    P, N, iters = xa.shape[0], xa.shape[1], int(max_iters)
-    total, off = workspace_layout(kind, P, N, iters)
-    if total > _WORKSPACE_LIMIT:
-        raise ValueError(f"score_hypotheses: {P} pairs need a {total >> 20} MiB workspace, over the {_WORKSPACE_LIMIT >> 20} MiB "
-                         "limit; call it on fewer pairs")
-    ws = torch.empty((total,), dtype=torch.uint8, device=xa.device)
-    S, R = _SMIN[kind], _SLOTS[kind]
-    if kind == KIND_E:
+    P = xa.shape[0]
+
+    def intrinsics():
+        if kind != KIND_E:
+            return ()
         if K_A is None or K_B is None:
             raise ValueError("score_hypotheses: model 'essential' needs K_A and K_B")
-        K = (_intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B"))
-        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, K, score)
+        return _intrinsics(K_A, P, xa.device, "K_A"), _intrinsics(K_B, P, xa.device, "K_B")
+
+    c, view, K = _inspect("score_hypotheses", kind, xa, xb, intrinsics, (), threshold, max_iters, score, seed)
+    if kind == KIND_E:
         T = _inverse_intrinsics(torch.stack(K, 1))
     else:
-        _hypotheses(xa, xb, kind, threshold, iters, _seed(seed), 0, ws, (), score)
-        norm = _view(ws, off, 0, torch.float64, (P, 2, 4))
+        norm = view(0, torch.float64, (2, 4))
         T = torch.zeros((P, 2, 3, 3), dtype=torch.float64, device=xa.device)
         T[:, :, 0, 0] = norm[:, :, 2]
         T[:, :, 1, 1] = norm[:, :, 2]
         T[:, :, 0, 2] = -norm[:, :, 2] * norm[:, :, 0]
         T[:, :, 1, 2] = -norm[:, :, 2] * norm[:, :, 1]
         T[:, :, 2, 2] = 1.0
-    return {
-        "samples": _view(ws, off, 2, torch.int32, (P, iters, S)).clone(),
-        "models": _view(ws, off, 3, torch.float64, (P, iters, R, 3, 3)).clone(),
-        "valid": _view(ws, off, 4, torch.int32, (P, iters, R)) != 0,
-        "cost": _view(ws, off, 7, torch.float64, (P, iters, R)).clone(),
-        "count": _view(ws, off, 8, torch.int32, (P, iters, R)).clone(),
-        "T_A": T[:, 0].clone(),
-        "T_B": T[:, 1].clone(),
-    }
+    return {"samples": c["samples"], "models": view(3, torch.float64, c["valid"].shape[1:] + (3, 3)).clone(), "valid": c["valid"],
+            "cost": c["cost"], "count": c["count"], "T_A": T[:, 0].clone(), "T_B": T[:, 1].clone()}
 
 
 # ------------------------------------------------------------------------------------------------------------ triangulation
@@ -1274,46 +1314,18 @@ def geometric_dist(depth1, depth2, T_1to2, K1, K2, dense_matches):
 
 # ------------------------------------------------------------------------------------------------------------ absolute pose
 CameraPose = RelativePose                 # what estimate_absolute_pose returns: the same R / t / Rt holder, t in world units
-_AP_SLOTS = 4
-_AP_REGIONS = 12
 _AP_RANSAC_OPT = {"max_reproj_error": 12.0, "max_iterations": 1000, "min_inliers": 3, "refine_iterations": 15}
 
 
 def _points3d(X, x):
     """X (N,3) or (P,N,3), x (N,2) or (P,N,2), fp32/fp64 device tensors -> contiguous (P,N,3), (P,N,2) fp64, single-pair flag"""
-    if X.dim() not in (2, 3) or X.shape[-1] != 3 or x.shape != X.shape[:-1] + (2,):
-        raise ValueError(f"expected world points (N,3) or (P,N,3) and pixels (N,2) or (P,N,2), got {tuple(X.shape)} and {tuple(x.shape)}")
-    for t in (X, x):
-        if t.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"points must be float32 or float64, got {t.dtype}")
-    single = X.dim() == 2
-    P, N = (1, X.shape[0]) if single else (X.shape[0], X.shape[1])
-    if N < 3:
-        raise ValueError(f"{N} matches, the minimal sample needs 3")
-    if P < 1:
-        raise ValueError("empty batch")
-    _need_gpu(X, x)
-    return X.reshape(P, N, 3).to(torch.float64).contiguous(), x.reshape(P, N, 2).to(torch.float64).contiguous(), single
+    return _prepare(X, x, 3, 2, _ENTRIES[_KIND_AP].smin,
+                    "expected world points (N,3) or (P,N,3) and pixels (N,2) or (P,N,2), got {0} and {1}", "points", "matches")
 
 
 def absolute_pose_workspace_layout(P, N, iters):
     """(total bytes, [region offsets]) of the workspace of roma_absolute_pose_hypotheses (include/roma_hip.h: 12 regions)"""
-    return _workspace_layout("roma_absolute_pose_workspace", _AP_REGIONS, P, N, iters)
-
-
-def _ap_chunks(P, N, iters):
-    """_chunks for the absolute-pose workspace"""
-    per_pair, _ = absolute_pose_workspace_layout(1, N, iters)
-    most = max(1, _WORKSPACE_LIMIT // per_pair)
-    n = -(-P // most)
-    step = -(-P // n)
-    return [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
-
-
-def _ap_hypotheses(Xc, xc, Kc, threshold, iters, score, seed, p0, ws):
-    check(_lib.load().roma_absolute_pose_hypotheses(Xc.data_ptr(), xc.data_ptr(), Kc.data_ptr(), Xc.shape[0], Xc.shape[1], iters,
-                                                    float(threshold), score, seed, p0, ws.data_ptr(), ws.numel(), _stream()),
-          "roma_absolute_pose_hypotheses")
+    return workspace_layout(_KIND_AP, P, N, iters)
 
 
 def find_absolute_pose(X, x, K, threshold=2.0, max_iters=1000, seed=None, lo_iters=3, refine_iters=0, *, scoring="msac"):
@@ -1335,21 +1347,10 @@ def find_absolute_pose(X, x, K, threshold=2.0, max_iters=1000, seed=None, lo_ite
     Xw, xp, single = _points3d(X, x)
     P, N = Xw.shape[0], Xw.shape[1]
     Kp = _intrinsics(K, P, Xw.device, "K")
-    iters, seed = int(max_iters), _seed(seed)
     R = torch.empty((P, 3, 3), dtype=torch.float64, device=Xw.device)
     t = torch.empty((P, 3), dtype=torch.float64, device=Xw.device)
     mask = torch.empty((P, N), dtype=torch.uint8, device=Xw.device)
-    lib = _lib.load()
-    chunks = _ap_chunks(P, N, iters)
-    # one workspace, sized for the widest chunk, serves every chunk in stream order (a narrower chunk's layout is no larger)
-    total, _ = absolute_pose_workspace_layout(max(b - a for a, b in chunks), N, iters)
-    ws = torch.empty((total,), dtype=torch.uint8, device=Xw.device)
-    for a, b in chunks:
-        Xc, xc, Kc = Xw[a:b], xp[a:b], Kp[a:b]
-        _ap_hypotheses(Xc, xc, Kc, threshold, iters, score, seed, a, ws)
-        check(lib.roma_absolute_pose_select(Xc.data_ptr(), xc.data_ptr(), Kc.data_ptr(), b - a, N, iters, float(threshold), score,
-                                            int(lo_iters), ws.data_ptr(), total, R[a:b].data_ptr(), t[a:b].data_ptr(),
-                                            mask[a:b].data_ptr(), _stream()), "roma_absolute_pose_select")
+    _ransac(_KIND_AP, Xw, xp, (Kp,), (), threshold, int(max_iters), score, _seed(seed), lo_iters, (R, t, mask))
     if refine_iters > 0:
         (R, t, mask), _ = _refine_absolute(R, t, Xw, xp, Kp, threshold, refine_iters, None)
     else:
@@ -1359,19 +1360,8 @@ def find_absolute_pose(X, x, K, threshold=2.0, max_iters=1000, seed=None, lo_ite
 
 def _refine_absolute(R, t, Xw, xp, Kp, threshold, iters, m):
     """roma_refine_absolute_pose on prepared (P,...) tensors -> (R, t, mask bool), (cost, count, steps)"""
-    P, N = Xw.shape[0], Xw.shape[1]
-    dev = Xw.device
-    Ro = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
-    to = torch.empty((P, 3), dtype=torch.float64, device=dev)
-    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
-    cost = torch.empty((P,), dtype=torch.float64, device=dev)
-    count = torch.empty((P,), dtype=torch.int32, device=dev)
-    steps = torch.empty((P,), dtype=torch.int32, device=dev)
-    check(_lib.load().roma_refine_absolute_pose(Xw.data_ptr(), xp.data_ptr(), Kp.data_ptr(), R.data_ptr(), t.data_ptr(),
-                                                None if m is None else m.data_ptr(), P, N, float(threshold), int(iters), Ro.data_ptr(),
-                                                to.data_ptr(), out.data_ptr(), cost.data_ptr(), count.data_ptr(), steps.data_ptr(),
-                                                _stream()), "roma_refine_absolute_pose")
-    return (Ro, to, out.bool()), (cost, count, steps)
+    return _run_refine("roma_refine_absolute_pose", (Xw, xp, Kp, R, t, m), Xw.shape[0], Xw.shape[1], (float(threshold), int(iters)),
+                       (3, 3), (3,))
 
 
 def refine_absolute_pose(R, t, X, x, K, threshold=2.0, iters=15, mask=None, return_info=False):
@@ -1487,89 +1477,33 @@ def absolute_pose_hypotheses(X, x, K, threshold=2.0, max_iters=1000, seed=0, *, 
     score = _scoring(scoring)
     _args(threshold, max_iters, 0)
     Xw, xp, _ = _points3d(X, x)
-    P, N, iters = Xw.shape[0], Xw.shape[1], int(max_iters)
-    Kp = _intrinsics(K, P, Xw.device, "K")
-    total, off = absolute_pose_workspace_layout(P, N, iters)
-    if total > _WORKSPACE_LIMIT:
-        raise ValueError(f"absolute_pose_hypotheses: {P} pairs need a {total >> 20} MiB workspace, over the {_WORKSPACE_LIMIT >> 20} MiB "
-                         "limit; call it on fewer pairs")
-    ws = torch.empty((total,), dtype=torch.uint8, device=Xw.device)
-    _ap_hypotheses(Xw, xp, Kp, threshold, iters, score, _seed(seed), 0, ws)
-    norm = _view(ws, off, 0, torch.float64, (P, 8))
+    Kp = _intrinsics(K, Xw.shape[0], Xw.device, "K")
+    h, view, _ = _inspect("absolute_pose_hypotheses", _KIND_AP, Xw, xp, lambda: (Kp,), (), threshold, max_iters, score, seed)
+    norm, valid = view(0, torch.float64, (8,)), h["valid"]
     c, s = norm[:, :3].clone(), norm[:, 3].clone()
-    R = _view(ws, off, 3, torch.float64, (P, iters, _AP_SLOTS, 3, 3)).clone()
-    tn = _view(ws, off, 9, torch.float64, (P, iters, _AP_SLOTS, 3))
-    valid = _view(ws, off, 4, torch.int32, (P, iters, _AP_SLOTS)) != 0
+    R = view(3, torch.float64, valid.shape[1:] + (3, 3)).clone()
+    tn = view(9, torch.float64, valid.shape[1:] + (3,))
     t = tn / s[:, None, None, None] - (R @ c[:, None, None, :, None]).squeeze(-1)
-    return {
-        "samples": _view(ws, off, 2, torch.int32, (P, iters, 3)).clone(),
-        "R": R,
-        "t": torch.where(valid[..., None], t, torch.zeros_like(t)),
-        "valid": valid,
-        "cost": _view(ws, off, 7, torch.float64, (P, iters, _AP_SLOTS)).clone(),
-        "count": _view(ws, off, 8, torch.int32, (P, iters, _AP_SLOTS)).clone(),
-        "centroid": c,
-        "scale": s,
-    }
+    return {"samples": h["samples"], "R": R, "t": torch.where(valid[..., None], t, torch.zeros_like(t)), "valid": valid,
+            "cost": h["cost"], "count": h["count"], "centroid": c, "scale": s}
 
 
 # ------------------------------------------------------------------------------------------------------ similarity registration
-_SIM_REGIONS = 12
-
-
 def _clouds(X, Y):
     """X, Y (N,3) or (P,N,3) fp32/fp64 device tensors of one shape -> contiguous (P,N,3) fp64 each, single-pair flag"""
-    if X.dim() not in (2, 3) or X.shape[-1] != 3 or Y.shape != X.shape:
-        raise ValueError(f"expected two clouds (N,3) or (P,N,3) of one shape, got {tuple(X.shape)} and {tuple(Y.shape)}")
-    for t in (X, Y):
-        if t.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"points must be float32 or float64, got {t.dtype}")
-    single = X.dim() == 2
-    P, N = (1, X.shape[0]) if single else (X.shape[0], X.shape[1])
-    if N < 3:
-        raise ValueError(f"{N} correspondences, the minimal sample needs 3")
-    if P < 1:
-        raise ValueError("empty batch")
-    _need_gpu(X, Y)
-    return X.reshape(P, N, 3).to(torch.float64).contiguous(), Y.reshape(P, N, 3).to(torch.float64).contiguous(), single
+    return _prepare(X, Y, 3, 3, _ENTRIES[_KIND_SIM].smin, "expected two clouds (N,3) or (P,N,3) of one shape, got {0} and {1}", "points",
+                    "correspondences")
 
 
 def similarity_workspace_layout(P, N, iters):
     """(total bytes, [region offsets]) of the workspace of roma_similarity_hypotheses (include/roma_hip.h: 12 regions)"""
-    return _workspace_layout("roma_similarity_workspace", _SIM_REGIONS, P, N, iters)
-
-
-def _sim_chunks(P, N, iters):
-    """_chunks for the similarity workspace"""
-    per_pair, _ = similarity_workspace_layout(1, N, iters)
-    most = max(1, _WORKSPACE_LIMIT // per_pair)
-    n = -(-P // most)
-    step = -(-P // n)
-    return [(p0, min(P, p0 + step)) for p0 in range(0, P, step)]
-
-
-def _sim_hypotheses(Xc, Yc, threshold, iters, score, with_scale, seed, p0, ws):
-    check(_lib.load().roma_similarity_hypotheses(Xc.data_ptr(), Yc.data_ptr(), Xc.shape[0], Xc.shape[1], iters, float(threshold), score,
-                                                 int(bool(with_scale)), seed, p0, ws.data_ptr(), ws.numel(), _stream()),
-          "roma_similarity_hypotheses")
+    return workspace_layout(_KIND_SIM, P, N, iters)
 
 
 def _refine_sim(s, R, t, Xw, Yw, threshold, iters, with_scale, m):
     """roma_refine_similarity on prepared (P,...) tensors -> (s, R, t, mask bool), (cost, count, steps)"""
-    P, N = Xw.shape[0], Xw.shape[1]
-    dev = Xw.device
-    so = torch.empty((P,), dtype=torch.float64, device=dev)
-    Ro = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
-    to = torch.empty((P, 3), dtype=torch.float64, device=dev)
-    out = torch.empty((P, N), dtype=torch.uint8, device=dev)
-    cost = torch.empty((P,), dtype=torch.float64, device=dev)
-    count = torch.empty((P,), dtype=torch.int32, device=dev)
-    steps = torch.empty((P,), dtype=torch.int32, device=dev)
-    check(_lib.load().roma_refine_similarity(Xw.data_ptr(), Yw.data_ptr(), s.data_ptr(), R.data_ptr(), t.data_ptr(),
-                                             None if m is None else m.data_ptr(), P, N, float(threshold), int(iters),
-                                             int(bool(with_scale)), so.data_ptr(), Ro.data_ptr(), to.data_ptr(), out.data_ptr(),
-                                             cost.data_ptr(), count.data_ptr(), steps.data_ptr(), _stream()), "roma_refine_similarity")
-    return (so, Ro, to, out.bool()), (cost, count, steps)
+    return _run_refine("roma_refine_similarity", (Xw, Yw, s, R, t, m), Xw.shape[0], Xw.shape[1],
+                       (float(threshold), int(iters), int(bool(with_scale))), (), (3, 3), (3,))
 
 
 def find_similarity(X, Y, threshold, max_iters=1000, seed=None, lo_iters=3, refine_iters=0, *, with_scale=True, scoring="msac"):
@@ -1591,24 +1525,14 @@ def find_similarity(X, Y, threshold, max_iters=1000, seed=None, lo_iters=3, refi
     _args(threshold, max_iters, lo_iters)
     Xw, Yw, single = _clouds(X, Y)
     P, N = Xw.shape[0], Xw.shape[1]
-    iters, seed = int(max_iters), _seed(seed)
     dev = Xw.device
     s = torch.empty((P,), dtype=torch.float64, device=dev)
     R = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
     t = torch.empty((P, 3), dtype=torch.float64, device=dev)
     mask = torch.empty((P, N), dtype=torch.uint8, device=dev)
     valid = torch.empty((P,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    chunks = _sim_chunks(P, N, iters)
-    # one workspace, sized for the widest chunk, serves every chunk in stream order (a narrower chunk's layout is no larger)
-    total, _ = similarity_workspace_layout(max(b - a for a, b in chunks), N, iters)
-    ws = torch.empty((total,), dtype=torch.uint8, device=dev)
-    for a, b in chunks:
-        Xc, Yc = Xw[a:b], Yw[a:b]
-        _sim_hypotheses(Xc, Yc, threshold, iters, score, with_scale, seed, a, ws)
-        check(lib.roma_similarity_select(Xc.data_ptr(), Yc.data_ptr(), b - a, N, iters, float(threshold), score, int(bool(with_scale)),
-                                         int(lo_iters), ws.data_ptr(), total, s[a:b].data_ptr(), R[a:b].data_ptr(), t[a:b].data_ptr(),
-                                         mask[a:b].data_ptr(), valid[a:b].data_ptr(), _stream()), "roma_similarity_select")
+    _ransac(_KIND_SIM, Xw, Yw, (), (int(bool(with_scale)),), threshold, int(max_iters), score, _seed(seed), lo_iters,
+            (s, R, t, mask, valid))
     if refine_iters > 0:
         (s, R, t, mask), _ = _refine_sim(s, R, t, Xw, Yw, threshold, refine_iters, with_scale, None)
     else:
@@ -1650,28 +1574,22 @@ def similarity_hypotheses(X, Y, threshold, max_iters=1000, seed=0, *, with_scale
     score = _scoring(scoring)
     _args(threshold, max_iters, 0)
     Xw, Yw, _ = _clouds(X, Y)
-    P, N, iters = Xw.shape[0], Xw.shape[1], int(max_iters)
-    total, off = similarity_workspace_layout(P, N, iters)
-    if total > _WORKSPACE_LIMIT:
-        raise ValueError(f"similarity_hypotheses: {P} pairs need a {total >> 20} MiB workspace, over the {_WORKSPACE_LIMIT >> 20} MiB "
-                         "limit; call it on fewer pairs")
-    ws = torch.empty((total,), dtype=torch.uint8, device=Xw.device)
-    _sim_hypotheses(Xw, Yw, threshold, iters, score, with_scale, _seed(seed), 0, ws)
-    norm = _view(ws, off, 0, torch.float64, (P, 8))
+    h, view, _ = _inspect("similarity_hypotheses", _KIND_SIM, Xw, Yw, lambda: (), (int(bool(with_scale)),), threshold, max_iters, score, seed)
+    norm, iters = view(0, torch.float64, (8,)), int(max_iters)
     cX, sX, cY, sY = norm[:, :3].clone(), norm[:, 3].clone(), norm[:, 4:7].clone(), norm[:, 7].clone()
-    R = _view(ws, off, 3, torch.float64, (P, iters, 3, 3)).clone()
-    ts = _view(ws, off, 9, torch.float64, (P, iters, 4))
-    valid = _view(ws, off, 4, torch.int32, (P, iters)) != 0
+    R = view(3, torch.float64, (iters, 3, 3)).clone()
+    ts = view(9, torch.float64, (iters, 4))
+    valid = h["valid"][..., 0]                                       # one slot per sample: no slot axis in what is returned
     s = ts[..., 3] * (sX / sY)[:, None]
     t = ts[..., :3] / sY[:, None, None] + cY[:, None, :] - s[..., None] * (R @ cX[:, None, :, None]).squeeze(-1)
     return {
-        "samples": _view(ws, off, 2, torch.int32, (P, iters, 3)).clone(),
+        "samples": h["samples"],
         "s": torch.where(valid, s, torch.zeros_like(s)),
         "R": R,
         "t": torch.where(valid[..., None], t, torch.zeros_like(t)),
         "valid": valid,
-        "cost": _view(ws, off, 7, torch.float64, (P, iters)).clone(),
-        "count": _view(ws, off, 8, torch.int32, (P, iters)).clone(),
+        "cost": h["cost"][..., 0],
+        "count": h["count"][..., 0],
         "centroid_X": cX, "scale_X": sX, "centroid_Y": cY, "scale_Y": sY,
     }
 

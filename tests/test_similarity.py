@@ -415,7 +415,7 @@ def test_find_similarity_is_deterministic_and_chunking_changes_no_bit(monkeypatc
     assert all(torch.equal(a, b[0]) for a, b in zip(single, whole["msac"]))      # pair 0 alone draws what it draws in the batch
     per_pair, _ = geometry.similarity_workspace_layout(1, 600, 200)
     monkeypatch.setattr(geometry, "_WORKSPACE_LIMIT", 2 * per_pair + 1024)
-    assert len(geometry._sim_chunks(5, 600, 200)) == 3
+    assert len(geometry._chunks(geometry._KIND_SIM, 5, 600, 200)) == 3
     for scoring in ("msac", "magsac"):
         assert all(torch.equal(a, b) for a, b in zip(whole[scoring], run(scoring))), scoring
 
