@@ -36,6 +36,14 @@ __device__ __forceinline__ Corner corners(float fx, float fy, int Hs, int Ws) {
   return c;
 }
 
+// A tap outside the source is loaded from a clamped address and must contribute nothing whatever lies there (an infinity or a NaN in
+// a border pixel included): its weight is 0 and of its elements only the sign bits are kept, so 0 * tap is the +-0 it is for any
+// finite tap and the sum keeps its bits.  The mask for the 32-bit words of a tap (one fp32 or two 16-bit elements each).
+template <typename T>
+__device__ __forceinline__ uint32_t tap_mask(bool valid) {
+  return valid ? 0xffffffffu : (sizeof(T) == 2 ? 0x80008000u : 0x80000000u);
+}
+
 // channels-last source and destination, C a multiple of the packet width
 template <typename T>
 __global__ __launch_bounds__(256) void warp_nhwc_kernel(const T* __restrict__ src, const float* __restrict__ flow,
@@ -53,15 +61,15 @@ __global__ __launch_bounds__(256) void warp_nhwc_kernel(const T* __restrict__ sr
     const float fx = flow[((size_t)(b * 2 + 0) * H + y) * W + x];
     const float fy = flow[((size_t)(b * 2 + 1) * H + y) * W + x];
     const Corner c = corners(fx, fy, Hs, Ws);
-    // all four taps are loaded unconditionally from clamped coordinates and masked through their weights: a guarded
-    // load would make hipcc branch and wait vmcnt(0) per tap (four serial L2 round trips)
+    // all four taps are loaded unconditionally from clamped coordinates and masked through their weights and tap_mask: a
+    // guarded load would make hipcc branch and wait vmcnt(0) per tap (four serial L2 round trips)
     const T* base = src + (size_t)((b + src_shift) % B) * Hs * Ws * src_pitch + (size_t)k * E16;
     const int xa = min(max(c.x0, 0), Ws - 1), xb = min(max(c.x0 + 1, 0), Ws - 1);
     const int ya = min(max(c.y0, 0), Hs - 1), yb = min(max(c.y0 + 1, 0), Hs - 1);
-    const u32x4 v00 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xa) * src_pitch);
-    const u32x4 v01 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xb) * src_pitch);
-    const u32x4 v10 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xa) * src_pitch);
-    const u32x4 v11 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xb) * src_pitch);
+    const u32x4 v00 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xa) * src_pitch) & tap_mask<T>(c.v00);
+    const u32x4 v01 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xb) * src_pitch) & tap_mask<T>(c.v01);
+    const u32x4 v10 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xa) * src_pitch) & tap_mask<T>(c.v10);
+    const u32x4 v11 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xb) * src_pitch) & tap_mask<T>(c.v11);
     const float w00 = c.v00 ? c.w00 : 0.f, w01 = c.v01 ? c.w01 : 0.f, w10 = c.v10 ? c.w10 : 0.f, w11 = c.v11 ? c.w11 : 0.f;
     float f00[E16], f01[E16], f10[E16], f11[E16], acc[E16];
     unpack16<T>(v00, f00);
@@ -102,12 +110,13 @@ __global__ __launch_bounds__(256) void warp_small_kernel(const T* __restrict__ s
     const T* p10 = base + ((size_t)yb * Ws + xa) * src_pitch;
     const T* p11 = base + ((size_t)yb * Ws + xb) * src_pitch;
     u32x4 v[4][NPK];
+    const uint32_t m00 = tap_mask<T>(c.v00), m01 = tap_mask<T>(c.v01), m10 = tap_mask<T>(c.v10), m11 = tap_mask<T>(c.v11);
 #pragma unroll
     for (int k = 0; k < NPK; ++k) {                              // unconditional, clamped: masked through the weights (see above)
-      v[0][k] = *reinterpret_cast<const u32x4*>(p00 + k * 8);
-      v[1][k] = *reinterpret_cast<const u32x4*>(p01 + k * 8);
-      v[2][k] = *reinterpret_cast<const u32x4*>(p10 + k * 8);
-      v[3][k] = *reinterpret_cast<const u32x4*>(p11 + k * 8);
+      v[0][k] = *reinterpret_cast<const u32x4*>(p00 + k * 8) & m00;
+      v[1][k] = *reinterpret_cast<const u32x4*>(p01 + k * 8) & m01;
+      v[2][k] = *reinterpret_cast<const u32x4*>(p10 + k * 8) & m10;
+      v[3][k] = *reinterpret_cast<const u32x4*>(p11 + k * 8) & m11;
     }
     const float w00 = c.v00 ? c.w00 : 0.f, w01 = c.v01 ? c.w01 : 0.f, w10 = c.v10 ? c.w10 : 0.f, w11 = c.v11 ? c.w11 : 0.f;
     T o[8 * NPK + 2];
@@ -318,10 +327,10 @@ __global__ __launch_bounds__(256) void assemble_packets_kernel(AsmParams p) {
       const T* base = src + (size_t)((b + p.src_shift) % p.B) * Hs * Ws * p.src_pitch + (size_t)k * 8;
       const int xa = min(max(c.x0, 0), Ws - 1), xb = min(max(c.x0 + 1, 0), Ws - 1);
       const int ya = min(max(c.y0, 0), Hs - 1), yb = min(max(c.y0 + 1, 0), Hs - 1);
-      const u32x4 v00 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xa) * p.src_pitch);
-      const u32x4 v01 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xb) * p.src_pitch);
-      const u32x4 v10 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xa) * p.src_pitch);
-      const u32x4 v11 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xb) * p.src_pitch);
+      const u32x4 v00 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xa) * p.src_pitch) & tap_mask<T>(c.v00);
+      const u32x4 v01 = *reinterpret_cast<const u32x4*>(base + ((size_t)ya * Ws + xb) * p.src_pitch) & tap_mask<T>(c.v01);
+      const u32x4 v10 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xa) * p.src_pitch) & tap_mask<T>(c.v10);
+      const u32x4 v11 = *reinterpret_cast<const u32x4*>(base + ((size_t)yb * Ws + xb) * p.src_pitch) & tap_mask<T>(c.v11);
       const float w00 = c.v00 ? c.w00 : 0.f, w01 = c.v01 ? c.w01 : 0.f, w10 = c.v10 ? c.w10 : 0.f, w11 = c.v11 ? c.w11 : 0.f;
       float f00[8], f01[8], f10[8], f11[8], acc[8];
       unpack16<T>(v00, f00);
@@ -376,10 +385,11 @@ __global__ __launch_bounds__(256) void assemble_9_6_kernel(AsmParams p) {
                        base + ((size_t)yb * Ws + xa) * p.src_pitch, base + ((size_t)yb * Ws + xb) * p.src_pitch};
     u32x4 v[4];
     uint32_t v8[4];
+    const uint32_t mask[4] = {tap_mask<T>(c.v00), tap_mask<T>(c.v01), tap_mask<T>(c.v10), tap_mask<T>(c.v11)};
 #pragma unroll
     for (int t = 0; t < 4; ++t) {                               // unconditional, clamped: masked through the weights
-      v[t] = *reinterpret_cast<const u32x4*>(tap[t]);
-      v8[t] = *reinterpret_cast<const uint32_t*>(tap[t] + 8);
+      v[t] = *reinterpret_cast<const u32x4*>(tap[t]) & mask[t];
+      v8[t] = *reinterpret_cast<const uint32_t*>(tap[t] + 8) & mask[t];
     }
     const float w00 = c.v00 ? c.w00 : 0.f, w01 = c.v01 ? c.w01 : 0.f, w10 = c.v10 ? c.w10 : 0.f, w11 = c.v11 ? c.w11 : 0.f;
     float f[4][C];

@@ -169,7 +169,8 @@ def local_correlation(feature0, feature1, local_radius, padding_mode="zeros", fl
 
 def warp_bilinear(src, flow, out=None, batch_shift=0):
     """F.grid_sample(src, flow.permute(0,2,3,1), mode='bilinear', align_corners=False) — matcher.py:109.
-    batch_shift: output item b samples src[(b + batch_shift) % B]."""
+    batch_shift: output item b samples src[(b + batch_shift) % B].  A tap outside src contributes 0 whatever src holds at its border
+    (inf and NaN included); a sample with all four taps outside, or with a NaN or infinite flow, is exactly 0."""
     _need_gpu(src, flow, out)
     B, C, Hs, Ws = src.shape
     _, _, H, W = flow.shape
